@@ -7,7 +7,15 @@ inputs resident in HBM: global scan over nR = 2000 rotations x nT = 151
 translations at the global-search radius (rU = 24, nPxl = 870), reseed, then
 10 particle-filter phases (mLR = 125, mLT = 9) -- SURVEY.md §8(d).  Weak
 scaling: every rank owns its own batch (gold-standard hemisphere = rank % 2),
-no collective on the expectation path.  Insert (mReco = 100), the RCCL
+no collective on the expectation path.
+
+A plain run sets up, warms up, times the steps and prints the result line
+(metric, value, ms_per_step, ...); --dump-outputs DIR also writes what the
+last timed step returned as DIR/<name>.npy (seeded inputs: the same arguments
+give the same inputs in every run).  Everything below is measured only with
+--full, beside the same headline figure.
+
+Insert (mReco = 100), the RCCL
 half-map all-reduce (thx_halfmap_allreduce over each hemisphere's ranks) and
 the FSC are timed separately and reported as extra fields.
 
@@ -26,7 +34,7 @@ PMC line traffic of the same launches (tools/l2_lines.py: TCP_TCC_READ_REQ x
 global scan and the full-resolution phase
 are reported beside it (roofline_scan, roofline_local).
 
-Launch: python bench.py [--gpus 1 --steps K --warmup W]
+Launch: python bench.py [--gpus 1 --steps K --warmup W] [--dump-outputs DIR] [--full]
         python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 import argparse
@@ -78,14 +86,48 @@ def parse():
     p.add_argument("--acg-iters", type=int, default=100, help="inferACG fixed-point iteration cap")
     p.add_argument("--large-first", type=int, default=0,
                    help="1: OPTIMISER_GLOBAL_PERTURB_LARGE (off in the reference's Config.h)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned (rank 0's "
+                        "particle clouds, weights, scores, classes and phase counts) to DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline figure: the pose-recovery check, the rooflines (HIP "
+                        "events around the phase kernel inside the timed steps, scan, "
+                        "full-resolution phase, insert), the FP32-scan step, the round end "
+                        "(insert, all-reduce, reconstruction, FSC) and the CPU baseline")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     p.add_argument("--cpu-images", type=int, default=4096,
                    help="images of the CPU-baseline sample (median of 3 runs)")
-    p.add_argument("--no-extras", action="store_true", help="skip insert / all-reduce / local roofline")
+    p.add_argument("--no-extras", action="store_true",
+                   help="with --full: skip insert / all-reduce / local roofline")
     p.add_argument("--no-rooflines", action="store_true",
-                   help="keep the insert and the round end (all-reduce, reconstruction, FSC) but "
-                        "skip the secondary rooflines (scan, full-resolution phase and insert)")
-    return p.parse_args()
+                   help="with --full: keep the insert and the round end (all-reduce, reconstruction, "
+                        "FSC) but skip the secondary rooflines (scan, full-resolution phase and insert)")
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps: at least one timed step")
+    return a
+
+
+DUMP_NAMES = ("quat", "trans", "pR", "pT", "score", "cls", "nPhase")   # Expectation.run's tuple
+DUMP_BYTES = 60 * 10 ** 6
+
+
+def dump_outputs(outs, path):
+    """The last timed step's outputs as `path`/<name>.npy: Expectation.run's
+    tuple over all sub-batches, float64 (score: float32).  Past DUMP_BYTES in all,
+    a fixed seeded sample of the images (the same rows of every array, listed
+    in image_index.npy)."""
+    os.makedirs(path, exist_ok=True)
+    arrs = [torch.cat([o[k] for o in outs]) for k in range(len(DUMP_NAMES))]
+    arrs = [x if x.dtype in (torch.float32, torch.float64) else x.to(torch.float64) for x in arrs]
+    n = arrs[0].shape[0]
+    per_image = sum(x[0].numel() * x.element_size() for x in arrs) + 8
+    keep = min(n, DUMP_BYTES // per_image)
+    idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False)) if keep < n else np.arange(n)
+    sel = torch.as_tensor(idx, device=arrs[0].device)
+    for name, x in zip(DUMP_NAMES, arrs):
+        np.save(os.path.join(path, name + ".npy"), x[sel].cpu().numpy())
+    np.save(os.path.join(path, "image_index.npy"), idx.astype(np.float64))
 
 
 def rank_layout(world, rank):
@@ -416,9 +458,10 @@ def main():
     chunk = a.chunk or a.images
     chunks = [(l0, min(a.images, l0 + chunk)) for l0 in range(0, a.images, chunk)]
     outs = [None] * len(chunks)
-    # HIP events around every k_local_fused launch of the timed steps (one launch
-    # per phase when the batch runs as one expectation call)
-    timer = ex.PhaseTimer(e, a.phases * max(1, a.steps)) if len(chunks) == 1 and a.phases else None
+    # --full: HIP events around every k_local_fused launch of the timed steps (one
+    # launch per phase when the batch runs as one expectation call)
+    timer = (ex.PhaseTimer(e, a.phases * a.steps)
+             if a.full and len(chunks) == 1 and a.phases else None)
 
     streams = [torch.cuda.Stream(dev) for _ in range(a.streams)] if a.streams > 1 else None
 
@@ -478,10 +521,12 @@ def main():
     local_ms = timer.ms() if timer is not None else []
     if timer is not None:
         timer.close()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(outs, a.dump_outputs)
 
     # accuracy sanity of the timed path: top rotation vs true pose
     res = {}
-    if rank == 0:
+    if a.full and rank == 0:
         # (off-grid poses: a 2000-rotation grid at the 15 A scan resolution
         # leaves about half the modes in a wrong basin; tools/diag_expect.py)
         qa = outs[0][0]
@@ -498,7 +543,7 @@ def main():
             "max_p10_p50_p90": [round(float(v), 2) for v in torch.quantile(ang.max(1).values, qs)]}
 
     extras = {}
-    traffic, traffic_src = pmc_traffic()
+    traffic, traffic_src = pmc_traffic() if a.full else ({}, None)
 
     def launch_traffic(key, ok):
         t = traffic.get(key) if ok else None
@@ -557,7 +602,7 @@ def main():
                     "LDS patch box serves it, so the line traffic (PMC, l2_line_*) runs at the roof "
                     "while the algorithmic rate is a fraction of it"}
 
-    if not a.no_extras and not a.no_rooflines:
+    if a.full and not a.no_extras and not a.no_rooflines:
         # ---- secondary: the global scan (bf16x6 MFMA) and its FP32-MFMA twin
         nRoof = min(ROOF_IMAGES, a.images)
         sec, issued, algorithmic, peak = scan_roofline(vol, px, gset, dat[:nRoof], ctf[:nRoof],
@@ -641,7 +686,7 @@ def main():
             "launch_ms": lsec * 1e3, "by_cloud": clouds}
         extras["insert_fullres"] = insert_fullres(vol, N, pf, dev)
 
-    if not a.no_extras:
+    if a.full and not a.no_extras:
         # ---- insert (mReco = 100) into the two hemispheres' half-maps, the
         # per-hemisphere RCCL all-reduce, FSC between the half-maps
         quat, trans = outs[0][0], outs[0][1]
@@ -777,7 +822,7 @@ def main():
             extras["reconstructed_fsc_shells_4_16_32_64"] = [round(float(fsc[k]), 4)
                                                            for k in (4, 16, 32, 64)]
 
-    if rank == 0 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and not a.no_cpu_baseline:
         vol_np = vol.cpu().numpy()
         n_cpu = min(a.cpu_images, dat.shape[0])
         extras["cpu_baseline"] = cpu_baseline(vol_np, N, pf, gset, dat[:n_cpu].cpu().numpy(),

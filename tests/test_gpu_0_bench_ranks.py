@@ -27,7 +27,7 @@ def test_bench_two_ranks_gloo_rehearsal():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", "--master-port=29517", os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "1", "--warmup", "0", "--box", "128", "--nr", "500",
-           "--images", "256", "--phases", "2", "--no-cpu-baseline", "--no-rooflines"]
+           "--images", "256", "--phases", "2", "--full", "--no-cpu-baseline", "--no-rooflines"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=100)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]

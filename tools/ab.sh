@@ -13,7 +13,7 @@ mkdir -p $O
 for t in "$@"; do
   lib=$R/thunder_amd/ab/lib_$t.so
   [ $t = prod ] && lib=$R/thunder_amd/libthunder_amd.so
-  THX_LIB=$lib timeout -k 10 300 python -u $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline \
+  THX_LIB=$lib timeout -k 10 300 python -u $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline \
       --no-extras > $O/${tag}_$t.json 2> $O/${tag}_$t.err
   python3 -c "import json; d=json.loads(open('$O/${tag}_$t.json').read().strip().splitlines()[-1]); print(json.dumps({'tag': '$t', 'value': d['value'], 'ms_per_step': d['ms_per_step'], 'phases': d['roofline']['launch_ms_by_phase']}))" >> $O/$tag.jsonl
 done

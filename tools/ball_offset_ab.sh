@@ -11,7 +11,7 @@ mkdir -p $O
 for k in $(seq $rounds); do
   for off in "$@"; do
     if [ "$off" = "-" ]; then unset THX_YPAIR_OFFSET; else export THX_YPAIR_OFFSET=$off; fi
-    timeout -k 10 300 python -u $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras \
+    timeout -k 10 300 python -u $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras \
         > $O/${tag}_run.json 2> $O/${tag}_run.err
     python3 -c "import json; d=json.loads(open('$O/${tag}_run.json').read().strip().splitlines()[-1]); print(json.dumps({'offset': '$off', 'round': $k, 'value': d['value'], 'ms_per_step': d['ms_per_step'], 'phases': d['roofline']['launch_ms_by_phase']}))" >> $O/$tag.jsonl
   done

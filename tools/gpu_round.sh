@@ -17,14 +17,14 @@ for s in $steps; do
       (cd $R && timeout -k 10 900 python -u -m pytest tests -m gpu -v --maxfail 15 --timeout 120 \
           --timeout-method thread > $O/tests.log 2>&1) ;;
     bench)
-      (cd $R && timeout -k 10 400 python -u bench.py > $O/bench.json 2> $O/bench.err) ;;
+      (cd $R && timeout -k 10 400 python -u bench.py --full > $O/bench.json 2> $O/bench.err) ;;
     prof)
       (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
           -d $O/prof -o run -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline \
           --no-extras > $O/prof.json 2> $O/prof.err)
       # the same command with the secondary kernels (scan / full-res / insert)
       (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
-          -d $O/prof_extras -o run -- python3 $R/bench.py --steps 1 --warmup 0 \
+          -d $O/prof_extras -o run -- python3 $R/bench.py --steps 1 --warmup 0 --full \
           --no-cpu-baseline > $O/prof_extras.json 2> $O/prof_extras.err) ;;
     pmc)
       # HBM bytes: FETCH_SIZE and WRITE_SIZE need separate passes (TCC slots);
@@ -39,7 +39,7 @@ for s in $steps; do
         [ $i = 4 ] && [ "$P3" = "$P" ] && break
         (cd /tmp && timeout -s KILL 240 rocprofv3 --pmc $P --output-format csv \
             --kernel-include-regex "k_scan|k_local|k_patch|k_insert|k_prep" \
-            -d $O/pmc$i -o run -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline \
+            -d $O/pmc$i -o run -- python3 $R/bench.py --steps 1 --warmup 0 --full --no-cpu-baseline \
             > $O/pmc$i.log 2>&1)
       done
       python3 $R/tools/traffic.py $O $O/traffic.json > /dev/null ;;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """HBM traffic per launch of the two roofline kernels, from the rocprofv3 PMC
 passes of tools/gpu_round.sh (pmc1 = FETCH_SIZE, pmc2 = WRITE_SIZE, both run
-on `bench.py --steps 1 --warmup 0`).
+on `bench.py --steps 1 --warmup 0 --full`).
 
 A "launch" is the whole launch sequence the bench times with HIP events
 (local_bench: the single k_local_fused<0> dispatch of a bench phase):
