@@ -847,6 +847,97 @@ int thx_pf_perturb2d(int nImg, int mR, int mT, double* rot, double* trans, doubl
                      double transM, unsigned long long seed, unsigned stream_id,
                      thx_stream_t stream);
 
+/* ------------------------------------------------------- noise model ---
+ * What Optimiser::maximization (src/Optimiser.cpp:3405-3559) does next to
+ * reconstructRef: allReduceSigma (:6395-6709), which makes the next round's
+ * _sigRcp, normCorrection (:6201-6393), initSigma (:5145-5243) and
+ * allocPreCal's sigRcpP rows (:8060-8071), under the reference's active
+ * switches (SIGMA_WHOLE_FREQUENCY, SIGMA_RANK1ST, CTF_ON_THE_FLY,
+ * RECENTRE_IMAGE_EACH_ITERATION, NORM_MASK; no SIGMA_MASK / SIGMA_GRADING, so
+ * w = 1; correctScale / refreshScale are compiled out there and absent here).
+ *
+ * Pose source: the reference takes Particle::rank1st per image.  These entry
+ * points take one pose per image from the caller -- quat / rot [nImg][4 / 2],
+ * trans [nImg][2], dF [nImg] (NULL = 1), cls [nImg] (NULL = class 0): the
+ * draw the caller inserts with (sample 0 of the resampled set, the
+ * reference's rand alternative at :6480) or its own top particle.
+ *
+ * thx_spectrum_pixels (host) -- the domain of powerSpectrum(dst, img, r)
+ *   (src/Functions/Spectrum.cpp:161-190), listed shell by shell: the stored
+ *   half-plane pixels j in [-r, r), i in [0, r] -- column 0 with j < 0
+ *   included, which a1 skips -- with i^2+j^2 < r^2 and u = rint(|(i,j)|) < r;
+ *   inside a shell in the reference's loop order (j outer, i inner).  iPxl as
+ *   a1; shellStart: r + 1 ints, shell u is [shellStart[u], shellStart[u+1]);
+ *   *nPxl = shellStart[r].  1 <= r <= idim/2 - 1.  Outputs may be NULL
+ *   (cap is then ignored: a size query).
+ * thx_power_spectrum -- ps[nImg][r] = powerSpectrum of a stack of
+ *   [idim][idim/2+1] Complex images (FP32 shell means).
+ * thx_residual_spectra / 2d -- per image l, P = the Fourier slice of class
+ *   cls[l] of the nK projectees at vol (Projector::project(Image&, rot, t),
+ *   src/Projector.cpp:167-183, 446-464; 2D: class images, bilinear),
+ *   M = CTF P(t), N = CTF P(t - offS_l), CTF from attr[l] at (dU d, dV d);
+ *   spectra[nImg][4][r] = shell means of |img - M|^2 (vSigM), |ori - N|^2
+ *   (vSigN), |M|^2 (sSVD), |img|^2 (dSVD).  oriFT may be NULL: row 1 is then
+ *   left untouched.  norm (may be NULL): norm[l] = sum |img_l - M|^2 over the
+ *   pixels with rL^2 <= i^2+j^2 < rNorm^2 (a bound on the pixel, not on the
+ *   shell; rNorm <= r - 1/2 so that the table holds them all), FP64.  A
+ *   class outside [0, nK) makes that image's outputs NaN.  One pass over the
+ *   table per image; results are bit-identical from run to run (a wave owns
+ *   whole shells and reduces them in table order; no atomics).
+ * thx_sigma_accumulate -- acc[3][nGroup][r+1] (FP64: sigM, sigN, svd sums,
+ *   the weight in column r) += the images' vSigM / 2, vSigN / 2,
+ *   sqrt(sSVD / dSVD) and 1 in row group[l] (0-based; NULL = row 0; a group
+ *   outside [0, nGroup) is skipped).  acc is NOT cleared, like F / T of the
+ *   insert; the images of one call are added in index order.  The caller
+ *   all-reduces acc over the hemisphere before
+ * thx_sigma_finalise (host) -- everything after the MPI_Allreduce: rows
+ *   divided by their weights (grouped = 0: row 0 serves every group), columns
+ *   r .. nCol-2 take column r-1, ratio = min(1, svd), sig = ratio sigM +
+ *   (1 - ratio) alpha sigN with alpha = sqrt(pi (maskRadius / (size
+ *   pixelSize))^2), sigRcp = -0.5 / sig on every column below nCol - 1 (the
+ *   last column of both is 0).  sig / sigRcp: FP64 [nGroup][nCol], nCol >=
+ *   r + 1.  As in the reference there is NO guard for an empty group or a
+ *   zero-power shell: those give inf / NaN.
+ * thx_sigma_init_accumulate -- initSigma's sums over this rank's images, in
+ *   image order, not cleared: avgSum[idim][idim/2+1][2] (FP64) += oriFT_l,
+ *   psSum[r] (FP64) += powerSpectrum(oriFT_l).
+ * thx_sigma_init_finalise (host) -- after the all-reduce: avg = avgSum /
+ *   nTotal, psAvg[u] = (ring mean of re + im of avg)^2, sig[.][u] =
+ *   (psSum[u] / nTotal - psAvg[u]) / 2 for every group, columns as above.
+ * thx_sig_rcp_rows -- out[l][i] = sigRcp[group[l]][iSig[i]] as float (group
+ *   NULL = row 0), the sigRcp argument of the scans and phases.
+ * thx_img_scale -- normCorrection's rescale: imgFT_l and oriFT_l (may be
+ *   NULL) *= scale[l] = sqrt(median(norm) / norm[l]). */
+int thx_spectrum_pixels(int idim, int r, int cap, int* iCol, int* iRow, int* iShell, int* iPxl,
+                        int* shellStart, int* nPxl);
+int thx_power_spectrum(const float* imgFT, int nImg, int idim, int r, const int* iPxl,
+                       const int* shellStart, float* ps, thx_stream_t stream);
+int thx_residual_spectra(const float* vol, int vdim, int pf, int nK, const float* imgFT,
+                         const float* oriFT, const float* attr, const double* quat,
+                         const double* trans, const double* offS, const double* dF,
+                         const int* cls, int nImg, int idim, int r, const int* iCol,
+                         const int* iRow, const int* iPxl, const int* shellStart, float* spectra,
+                         double* norm, float rL, float rNorm, thx_stream_t stream);
+int thx_residual_spectra2d(const float* vol, int vdim, int pf, int nK, const float* imgFT,
+                           const float* oriFT, const float* attr, const double* rot,
+                           const double* trans, const double* offS, const double* dF,
+                           const int* cls, int nImg, int idim, int r, const int* iCol,
+                           const int* iRow, const int* iPxl, const int* shellStart, float* spectra,
+                           double* norm, float rL, float rNorm, thx_stream_t stream);
+int thx_sigma_accumulate(const float* spectra, const int* group, int nImg, int r, int nGroup,
+                         double* acc, thx_stream_t stream);
+int thx_sigma_finalise(const double* acc, int nGroup, int r, int nCol, double alpha, int grouped,
+                       double* sig, double* sigRcp);
+int thx_sigma_init_accumulate(const float* oriFT, int nImg, int idim, int r, const int* iPxl,
+                              const int* shellStart, double* avgSum, double* psSum,
+                              thx_stream_t stream);
+int thx_sigma_init_finalise(const double* avgSum, const double* psSum, double nTotal, int idim,
+                            int r, int nGroup, int nCol, double* sig, double* sigRcp);
+int thx_sig_rcp_rows(const double* sigRcp, int nGroup, int nCol, const int* group, const int* iSig,
+                     int nPxl, int nImg, float* out, thx_stream_t stream);
+int thx_img_scale(float* imgFT, float* oriFT, const float* scale, int nImg, int idim,
+                  thx_stream_t stream);
+
 /* HIP event pairs for thx_expect_cfg.phaseEvents: create n (begin, end)
  * pairs, read back ms[i] per pair (-1: not recorded), destroy. */
 int thx_event_pairs_create(int n, void** events);
