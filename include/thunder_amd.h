@@ -938,6 +938,57 @@ int thx_sig_rcp_rows(const double* sigRcp, int nGroup, int nCol, const int* grou
 int thx_img_scale(float* imgFT, float* oriFT, const float* scale, int nImg, int idim,
                   thx_stream_t stream);
 
+/* ------------------------------------------- the next round's projectee ---
+ * The reconstructed reference of box N (thx_reconstruct's dst or dstFT) ->
+ * the half-complex projectee of box vdim = pf N that the expectation reads,
+ * on device (csrc/refresh.hip).  Real maps: [k][j][i], origin at index 0,
+ * negatives wrapped; Fourier maps: [k][j][i <= box/2] complex.
+ *
+ * thx_ref_average -- Model::compareTwoHemispheres' averaging
+ *   (src/Model.cpp:611-690) on nK Fourier maps of box N (mode3d 1:
+ *   [N][N][N/2+1], test QUAD_3(i,j,k) < r^2, :660-669; mode3d 0: images
+ *   [N][N/2+1], test QUAD(i,j) < r^2, :647-656), in place: A = B = (A + B) / 2
+ *   below r; r < 0 averages everything (K > 1 or no gold standard, :683-689);
+ *   B NULL skips the averaging.  Then lowPassFilter(thres, ew)
+ *   (src/Functions/Filter.cpp:46-92; f = |(i,j,k)| / N, solventFlatten calls
+ *   it with thres = r / size, ew = EDGE_WIDTH_FT / size under
+ *   OPTIMISER_SOLVENT_FLATTEN_LOW_PASS, which include/Config.h:173-181 leaves
+ *   out): thres <= 0 turns it off.  One pass, one thread per stored voxel.
+ * thx_projectee_workspace (host) -- bytes thx_projectee needs; 0 for bad
+ *   arguments (method 2 on a box the pruned path does not serve included).
+ * thx_projectee -- Optimiser::solventFlatten (src/Optimiser.cpp:7768-7989
+ *   with OPTIMISER_SOLVENT_FLATTEN_MASK_ZERO: softMask(dst, src, rMask, edge,
+ *   bg = 0), src/Functions/Mask.cpp:499-521, or the provided mask dst = src
+ *   (1 - (1 - alpha)), :533-544) and Model::refreshProj ->
+ *   Projector::setProjectee (src/Model.cpp:1013-1044, src/Projector.cpp:
+ *   97-148): VOL_PAD_RL (include/Image/ImageFunctions.h:176-192),
+ *   gridCorrection (src/Projector.cpp:524-606: / TIK_RL(|r| / (pf vdim)), the
+ *   padded box; interp 1: NIK_RL), FFT::fw unnormalised.  src: the real map
+ *   [N^3] (fromFT 0) or its transform [N][N][N/2+1] (fromFT 1: FFT::bw runs
+ *   first).  rMask <= 0 and alphaMask NULL: no mask; both given: rejected.
+ *   dst [vdim][vdim][vdim/2+1] complex = scale x the reference's projectee
+ *   (scale 1: as the reference; N^-1.5: the normalisation of the synthetic
+ *   projectees).  method 0: the measured choice, 1: fused pad + hipFFT's 3D
+ *   plan (any box), 2: the pruned LDS passes (power-of-two vdim in [16, 512],
+ *   else rejected).  dst must not overlap src, alphaMask or the workspace.
+ *   Stream-ordered, no host synchronisation, no atomics: bit-identical from
+ *   run to run.
+ * thx_projectee2d -- the same for nK class images [nK][N][N] (or
+ *   [nK][N][N/2+1] with fromFT) -> [nK][vdim][vdim/2+1]: radial mask over
+ *   |(i,j)| (src/Optimiser.cpp:7933-7957; a provided mask aborts there and is
+ *   rejected here), IMG_PAD_RL, / TIK_RL(|(i,j)| / (pf vdim))
+ *   (src/Projector.cpp:537-556), batched 2D transform. */
+int thx_ref_average(float* A, float* B, int N, int nK, float r, float thres, float ew, int mode3d,
+                    thx_stream_t stream);
+size_t thx_projectee_workspace(int N, int pf, int method, int fromFT);
+int thx_projectee(const float* src, int fromFT, int N, int pf, float rMask, float edge,
+                  const float* alphaMask, int interp, float scale, float* dst, int method,
+                  void* workspace, size_t wsBytes, thx_stream_t stream);
+size_t thx_projectee2d_workspace(int N, int pf, int nK, int fromFT);
+int thx_projectee2d(const float* src, int fromFT, int nK, int N, int pf, float rMask, float edge,
+                    const float* alphaMask, int interp, float scale, float* dst, void* workspace,
+                    size_t wsBytes, thx_stream_t stream);
+
 /* HIP event pairs for thx_expect_cfg.phaseEvents: create n (begin, end)
  * pairs, read back ms[i] per pair (-1: not recorded), destroy. */
 int thx_event_pairs_create(int n, void** events);

@@ -115,6 +115,19 @@ THX_DEV void fft_stages(float2* a, int off, const float2* __restrict__ tw, float
     }
 }
 
+// blockIdx.x -> tile (-1: past the end) with runs of consecutive tiles on
+// one XCD: dispatch deals workgroups round-robin over the 8 XCDs, and the
+// kx-neighbouring tiles of a column pass share 128-byte lines (a tile row is
+// 128 bytes of a row of N / 2 + 1 complex, so it straddles two), which are
+// then fetched and written back once per XCD's L2.  Launch
+// (ntiles + 7) / 8 * 8 blocks.
+THX_DEV int xcd_tile(int ntiles)
+{
+    const int per = (ntiles + 7) / 8;
+    const int t = (int)(blockIdx.x % 8) * per + (int)(blockIdx.x / 8);
+    return t < ntiles ? t : -1;
+}
+
 // In place on the padded column (col, off); tw: e^{-2 pi i q / N}, q < N.
 // The caller makes the column's data visible to the wave first.
 template <int N>

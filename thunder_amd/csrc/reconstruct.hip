@@ -41,16 +41,15 @@
 
 #include "common.h"
 #include "fft_lds.h"
+#include "fft_plans.h"
 
-#define THX_FFT(call)                                                          \
-    do {                                                                       \
-        hipfftResult r_ = (call);                                              \
-        if (r_ != HIPFFT_SUCCESS) {                                            \
-            ::thx::set_error("%s:%d %s: hipfft error %d", __FILE__, __LINE__, \
-                             #call, (int)r_);                                  \
-            return THX_ERR_HIP;                                                \
-        }                                                                      \
-    } while (0)
+using thx::Plans;
+using thx::PlanEntry;
+using thx::Plans2;
+using thx::cached_plans;
+using thx::c2r3d;
+using thx::r2c3d;
+using thx::plans2d;
 
 namespace {
 
@@ -379,12 +378,7 @@ __global__ void k_sym_planes(float* __restrict__ T, int vdim)
 // one XCD: dispatch deals workgroups round-robin over the 8 XCDs, and the
 // kx-neighbouring tiles of the column passes share the 128-byte lines of
 // T and W (a tile row of floats is 64 bytes), read once per XCD's L2.
-THX_DEV int even_tile(int ntiles)
-{
-    const int per = (ntiles + 7) / 8;
-    const int t = (int)(blockIdx.x % 8) * per + (int)(blockIdx.x / 8);
-    return t < ntiles ? t : -1;
-}
+THX_DEV int even_tile(int ntiles) { return thx::xcd_tile(ntiles); }
 
 // z columns.  INIT: C = T W (W as k_init_w left it) -> R2C (+) along z.
 // Otherwise first the C2R (-) along z of G's Hermitian nz-half: the balanced
@@ -661,14 +655,6 @@ double mkb_rl_r2(double r2, double a, double alpha)
     return std::pow(2 * M_PI, 1.5) * a * a * a / bessel_i0(alpha) * nu15_over(v, in);
 }
 
-struct Plans {
-    hipfftHandle c2r = 0, r2c = 0, r2cN = 0;
-    hipfftHandle c2rX = 0, r2cX = 0;     // 1D batched along x (the column-pass transforms)
-    float2* tw = nullptr;                // vdim twiddles exp(-2 pi i k / vdim)
-    bool cols = false;                   // the column-pass transforms are available
-    size_t work = 0;
-};
-
 // The column-pass 3D transforms: power-of-two vdim whose LDS tile fits
 bool col_fft_ok(int vdim)
 {
@@ -748,7 +734,9 @@ int col_pass(const Plans& p, float2* C, int vdim, bool inv, bool zAxis, hipStrea
     return THX_OK;
 }
 
-int c2r3d(const Plans& p, float2* C, float* rl, int vdim, hipStream_t s, int method = 0)
+}  // namespace
+
+int thx::c2r3d(const Plans& p, float2* C, float* rl, int vdim, hipStream_t s, int method)
 {
     if (!use_cols(p, method)) {
         THX_FFT(hipfftExecC2R(p.c2r, reinterpret_cast<hipfftComplex*>(C), rl));
@@ -761,7 +749,7 @@ int c2r3d(const Plans& p, float2* C, float* rl, int vdim, hipStream_t s, int met
     return THX_OK;
 }
 
-int r2c3d(const Plans& p, float* rl, float2* C, int vdim, hipStream_t s, int method = 0)
+int thx::r2c3d(const Plans& p, float* rl, float2* C, int vdim, hipStream_t s, int method)
 {
     if (!use_cols(p, method)) {
         THX_FFT(hipfftExecR2C(p.r2c, rl, reinterpret_cast<hipfftComplex*>(C)));
@@ -773,19 +761,9 @@ int r2c3d(const Plans& p, float* rl, float2* C, int vdim, hipStream_t s, int met
     return st;
 }
 
-// Plans per (device, vdim, N, stream), made once: creating a 512^3 hipFFT
-// plan costs hundreds of ms, the transforms themselves ~0.6 ms.  A plan binds
-// one stream and work area, so every stream has its own; calls on one stream
-// take its entry's mutex (host threads sharing a stream), calls on different
-// streams -- the two hemispheres, several GPUs -- run concurrently.  The
-// cache's own mutex covers only the lookup.
-struct PlanEntry {
-    std::mutex mu;
-    Plans p;
-    bool made = false;
-    unsigned* bits = nullptr;   // pinned host word: the balancing loop's read-back
-};
+namespace {
 
+// the cache of PlanEntry (fft_plans.h)
 struct PlanCache {
     std::mutex mu;
     std::map<std::tuple<int, int, int, hipStream_t>, std::unique_ptr<PlanEntry>> plans;
@@ -797,9 +775,11 @@ PlanCache& plan_cache()
     return *c;
 }
 
+}  // namespace
+
 // the entry for (current device, vdim, N, s), its plans made; returned locked
-int cached_plans(int vdim, int N, hipStream_t s, PlanEntry** out,
-                 std::unique_lock<std::mutex>& lock)
+int thx::cached_plans(int vdim, int N, hipStream_t s, PlanEntry** out,
+                      std::unique_lock<std::mutex>& lock)
 {
     int dev = 0;
     THX_HIP(hipGetDevice(&dev));
@@ -821,6 +801,8 @@ int cached_plans(int vdim, int N, hipStream_t s, PlanEntry** out,
     *out = e;
     return THX_OK;
 }
+
+namespace {
 
 // the tabulated real-space kernel per (a, alpha), computed once (1e5 Bessel
 // evaluations) under its own lock
@@ -1209,11 +1191,9 @@ __global__ void k2_normalise_first(float* __restrict__ F, float* __restrict__ T,
     *f = make_float2(f->x * sf, f->y * sf);
 }
 
-struct Plans2 {
-    hipfftHandle c2r = 0, r2c = 0;
-};
+}  // namespace
 
-int plans2d(int vdim, int nK, hipStream_t s, Plans2** out, std::unique_lock<std::mutex>& lock)
+int thx::plans2d(int vdim, int nK, hipStream_t s, Plans2** out, std::unique_lock<std::mutex>& lock)
 {
     static std::mutex mu;
     static std::map<std::tuple<int, int, int, hipStream_t>, std::unique_ptr<std::pair<std::mutex, Plans2>>>*
@@ -1240,8 +1220,6 @@ int plans2d(int vdim, int nK, hipStream_t s, Plans2** out, std::unique_lock<std:
     *out = &p;
     return THX_OK;
 }
-
-}  // namespace
 
 extern "C" int thx_prepare_tf2d(float* F, float* T, int vdim, int nK, thx_stream_t stream)
 {
