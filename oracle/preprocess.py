@@ -14,8 +14,10 @@ OPTIMISER_INIT_IMG_NORMALISE_OUT_MASK_REGION, include/Config.h:184, 190):
     stddev(0, img) (:543-547), regionMean(img, r, 0) (src/Functions/Mask.cpp:
     102-127);
   maskImg with zeroMask (:4964-4996) -> softMask(dst, src, r, ew, 0)
-    (src/Functions/Mask.cpp:363-385), normaliseImg (:4998-5012), fwImg (FFTW
-    r2c, unnormalised);
+    (src/Functions/Mask.cpp:363-385), or without it the noise background
+    softMask(dst, src, r, ew, 0, _stdN) (Mask.cpp:387-417) with the Gaussian
+    draws passed in, normaliseImg (:4998-5012), fwImg (FFTW r2c,
+    unnormalised);
   reMaskImg (:6093-6150): backward FFT / N^2, x softMask(mask, r, ew)
     (Mask.cpp:333-350), forward.
 """
@@ -65,15 +67,49 @@ def soft_mask_keep(N, r, ew=EDGE_WIDTH_RL):
     return np.where(u < r, 1.0, np.where(u > r + ew, 0.0, 1.0 - w))
 
 
-def finish(img, r, std_n, ew=EDGE_WIDTH_RL):
-    """zeroMask softMask + 1 / stdN + forward FFT -> (imgFT, oriFT)."""
+def masked_image(img, r, std_n, ew=EDGE_WIDTH_RL, draws=None):
+    """maskImg + normaliseImg in real space, float64; img [..., N, N].
+    draws None: zeroMask, softMask(dst, src, r, ew, 0).  Otherwise the
+    noise background softMask(dst, src, r, ew, bgMean = 0, bgStd = stdN)
+    (src/Functions/Mask.cpp:387-417): draws holds one standard normal per
+    pixel (the caller's generator; the reference's is GSL's), the background
+    draw * stdN replaces the image past r + ew and is blended in by the
+    cosine weight over [r, r + ew]; inside r the draw is not used."""
     N = img.shape[-1]
     keep = soft_mask_keep(N, r, ew)
-    m = img.astype(np.float64) * keep / std_n
+    x = img.astype(np.float64)
+    if draws is None:
+        return x * keep / std_n
+    bg = np.asarray(draws, np.float64) * std_n
+    return (bg * (1.0 - keep) + x * keep) / std_n
+
+
+def finish(img, r, std_n, ew=EDGE_WIDTH_RL, draws=None):
+    """softMask (zeroMask, or the noise background from draws) + 1 / stdN +
+    forward FFT -> (imgFT, oriFT)."""
     o = img.astype(np.float64) / std_n
-    return np.fft.rfft2(m), np.fft.rfft2(o)
+    return np.fft.rfft2(masked_image(img, r, std_n, ew, draws)), np.fft.rfft2(o)
+
+
+def remask_image(ft, N, r, ew=EDGE_WIDTH_RL):
+    """reMaskImg up to its forward transform: the re-masked real-space image."""
+    rl = np.fft.irfft2(ft, s=(N, N))          # numpy's inverse is FFTW's backward / N^2
+    return rl * soft_mask_keep(N, r, ew)
 
 
 def remask(ft, N, r, ew=EDGE_WIDTH_RL):
-    rl = np.fft.irfft2(ft, s=(N, N))          # numpy's inverse is FFTW's backward / N^2
-    return np.fft.rfft2(rl * soft_mask_keep(N, r, ew))
+    return np.fft.rfft2(remask_image(ft, N, r, ew))
+
+
+# The real-space comparison of a half-complex result with a float64 image: a
+# wrong mask weight at one pixel stays at that pixel here, where in Fourier
+# space it is spread over every coefficient and measured against the DC term.
+RL_TOL_MAX = 1e-5          # no tolerance of this comparison may exceed it
+
+
+def rl_error(ft, ref_rl):
+    """max |irfft2(ft) - ref| / max |ref| per image, in float64; ft
+    [..., N, N/2+1] half-complex (unnormalised forward), ref_rl [..., N, N]."""
+    ref = np.asarray(ref_rl, np.float64)
+    rl = np.fft.irfft2(np.asarray(ft).astype(np.complex128), s=ref.shape[-2:])
+    return np.abs(rl - ref).max(axis=(-2, -1)) / np.abs(ref).max(axis=(-2, -1))

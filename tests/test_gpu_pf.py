@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from philox_ref import _philox_4x32_10
 from thunder_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -75,22 +76,6 @@ def test_shuffle_is_uniform():
     chi2 = ((counts - exp) ** 2 / exp).sum()
     dof = (nIn - 1) ** 2
     assert chi2 < dof + 5 * np.sqrt(2 * dof), chi2
-
-
-def _philox_4x32_10(seed, a, b, c, d):
-    """Philox-4x32-10 as thunder_amd/csrc/common.h's Philox::next() draws it:
-    counter (a, b, c, d), key = the 64-bit seed's halves; numpy uint64
-    arithmetic on arrays of counters."""
-    M0, M1, W0, W1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), 0x9E3779B9, 0xBB67AE85
-    m32 = np.uint64(0xFFFFFFFF)
-    x = [np.asarray(v, np.uint64) & m32 for v in (a, b, c, d)]
-    k0, k1 = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
-    for _ in range(10):
-        p0, p1 = M0 * x[0], M1 * x[2]
-        x = [((p1 >> np.uint64(32)) ^ x[1] ^ np.uint64(k0)) & m32, p1 & m32,
-             ((p0 >> np.uint64(32)) ^ x[3] ^ np.uint64(k1)) & m32, p0 & m32]
-        k0, k1 = (k0 + W0) & 0xFFFFFFFF, (k1 + W1) & 0xFFFFFFFF
-    return x
 
 
 @pytest.mark.parametrize("nIn", [8, 100, 256, 300, 2000])

@@ -7,6 +7,7 @@ import struct
 import numpy as np
 import pytest
 
+import philox_ref
 from oracle import preprocess as opp
 from thunder_amd import io
 
@@ -110,3 +111,94 @@ def test_preprocess_restatement_known_answers():
     # re-masking an image supported inside r changes nothing
     inner = np.where(u < r, out, 0).astype(np.float64)
     assert np.allclose(opp.remask(np.fft.rfft2(inner), N, r), np.fft.rfft2(inner), atol=1e-9)
+
+
+def _normalised_image(N, r, seed):
+    """A smooth blob plus noise with an offset and a gain, through substractBgImg."""
+    rng = np.random.default_rng(seed)
+    i, j = opp.rl_coords(N)
+    blob = np.exp(-(i ** 2 + j ** 2) / (2 * (N / 6.0) ** 2))
+    img = (1.7 * (3 * blob + 0.5 * rng.standard_normal((N, N))) + 2.0).astype(np.float32)
+    out, st = opp.stats_and_normalise(img, r)
+    return out, float(st[2])
+
+
+def test_noise_mask_restatement_known_answers():
+    """softMask(dst, src, r, ew, bgMean = 0, bgStd = stdN) then 1 / stdN, at
+    N = 32, r = 7, ew = 6, where lattice points lie on r, on r + ew / 2 = 10
+    and on r + ew = 13: inside r the pixel is untouched, on r the background's
+    weight is 0, half-way it is the half-and-half blend, on and beyond r + ew
+    it is draw * stdN / stdN; with all draws zero it is the zero mask; finish
+    is the rfft2 of the masked image in both modes."""
+    N, r, ew = 32, 7.0, 6.0
+    x, std_n = _normalised_image(N, r, 11)
+    g = np.random.default_rng(12).standard_normal((N, N))
+    m = opp.masked_image(x, r, std_n, ew, draws=g)
+    i, j = opp.rl_coords(N)
+    u = np.hypot(i, j)
+    xs = x.astype(np.float64) / std_n
+    assert (u < r).sum() > 100 and np.array_equal(m[u < r], xs[u < r])
+    assert (u == r).sum() == 4 and np.allclose(m[u == r], xs[u == r], rtol=0, atol=1e-15)
+    assert (u > r + ew).sum() > 100
+    assert np.allclose(m[u > r + ew], (g * std_n / std_n)[u > r + ew], rtol=1e-15, atol=0)
+    assert (u == r + ew).sum() == 12 and np.allclose(m[u == r + ew], g[u == r + ew], rtol=1e-12)
+    half = u == r + ew / 2
+    assert half.sum() == 12 and np.allclose(m[half], 0.5 * g[half] + 0.5 * xs[half], rtol=0, atol=1e-12)
+    edge = (u > r) & (u < r + ew)
+    w = (m[edge] - xs[edge]) / (g[edge] - xs[edge])          # the background's portion
+    assert np.all((w > 0) & (w < 1))
+    zero = opp.masked_image(x, r, std_n, ew)
+    assert np.array_equal(opp.masked_image(x, r, std_n, ew, draws=np.zeros((N, N))), zero)
+    assert np.allclose(zero, xs * opp.soft_mask_keep(N, r, ew), rtol=1e-15, atol=0)
+    for d in (None, g):
+        ft, oft = opp.finish(x, r, std_n, ew, draws=d)
+        assert np.array_equal(ft, np.fft.rfft2(opp.masked_image(x, r, std_n, ew, draws=d)))
+        assert np.array_equal(oft, np.fft.rfft2(xs))
+    # re-masking: remask is the rfft2 of remask_image
+    assert np.array_equal(opp.remask(ft, N, r, ew), np.fft.rfft2(opp.remask_image(ft, N, r, ew)))
+
+
+def test_philox_restatement_known_answers():
+    """Philox-4x32-10 at Random123's published vectors, uniform's 53-bit
+    construction, and the mask stream's Box-Muller normals: mean and sd over
+    the 513 x 32 x 32 draws of seed 1 within 5 standard errors of 0 and 1."""
+    x = philox_ref._philox_4x32_10(0, 0, 0, 0, 0)
+    assert [int(v) for v in x] == [0x6627E8D5, 0xE169C58D, 0xBC57AC4C, 0x9B00DBD8]
+    f = 0xFFFFFFFF
+    x = philox_ref._philox_4x32_10((f << 32) | f, f, f, f, f)
+    assert [int(v) for v in x] == [0x408F276D, 0x41C83B0E, 0xA20BC7C6, 0x6D5451FD]
+    # counter 0, key 0: x = 0x6627e8d5, y = 0xe169c58d
+    m = ((0x6627E8D5 << 21) ^ 0xE169C58D) & ((1 << 53) - 1)
+    assert philox_ref.uniform(0, 0, 0, 0, 0) == (m + 0.5) / 2.0 ** 53
+    u1, u2 = philox_ref.uniform(5, 1, 2, 3, 0), philox_ref.uniform(5, 1, 2, 3, 1)
+    assert philox_ref.gauss(5, 1, 2, 3) == np.sqrt(-2 * np.log(u1)) * np.cos(2 * np.pi * u2)
+    g = philox_ref.mask_draws(1, 513, 32)
+    n = g.size
+    assert g.shape == (513, 32, 32) and np.all(np.isfinite(g))
+    assert abs(g.mean()) < 5 / np.sqrt(n) and abs(g.std() - 1) < 5 / np.sqrt(2 * n)
+    # pixel q's stream does not depend on the stack's size; another seed is another stream
+    assert np.array_equal(philox_ref.mask_draws(1, 2, 32), g[:2])
+    assert not np.any(philox_ref.mask_draws(2, 2, 32) == g[:2])
+
+
+def test_real_space_comparison_sees_one_wrong_mask_weight():
+    """Why tests/test_gpu_preprocess.py compares in real space: one edge
+    pixel's mask weight off by 1e-3 (N = 36, r = 11.7, ew = 6) moves the
+    Fourier output by less than the 2e-5 x max bound of
+    test_gpu_ingest.py::test_preprocess_matches_restatement, because every
+    coefficient is measured against the DC term; brought back with irfft2 the
+    error stays at its pixel and fails the real-space bound, while a correct
+    float32 output passes it."""
+    N, r, ew = 36, 11.7, 6.0
+    x, std_n = _normalised_image(N, r, 7)
+    ref = opp.masked_image(x, r, std_n, ew)
+    keep = opp.soft_mask_keep(N, r, ew)
+    edge = (keep > 0.2) & (keep < 0.8)
+    p = np.unravel_index(np.argmax(np.where(edge, np.abs(x), 0)), x.shape)
+    wrong = keep.copy()
+    wrong[p] += 1e-3
+    ft_ref = np.fft.rfft2(ref)
+    ft_bad = np.fft.rfft2(x.astype(np.float64) * wrong / std_n).astype(np.complex64)
+    assert np.abs(ft_bad - ft_ref).max() <= 2e-5 * np.abs(ft_ref).max()          # unseen
+    assert opp.rl_error(ft_bad, ref) > 10 * opp.RL_TOL_MAX                       # seen
+    assert opp.rl_error(ft_ref.astype(np.complex64), ref) < 0.1 * opp.RL_TOL_MAX
