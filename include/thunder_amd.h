@@ -73,6 +73,20 @@ int thx_pixel_set(int idim, int pf, float rU, float rL, int cap, int* iCol,
 int thx_pixel_tile_order(const int* iCol, const int* iRow, int nPxl, int cap,
                          int* order, int* nOrd);
 
+/* The tile order without its all-padding steps: every aligned 4-entry step
+ * of `order` (nOrd ints, a multiple of 4) whose entries are all -1 is
+ * removed, every other step kept unchanged and in sequence, and the end
+ * padded with -1 to a multiple of 32.  The box-less local-phase kernels visit
+ * the pixels in this order (they build it themselves on the device from
+ * pxOrder: callers keep passing the tile order); a removed step adds exactly
+ * zero, so the phase's outputs are bit for bit those of the tile order.
+ * Host function; out: cap ints (may be NULL), *nOut receives the length
+ * (<= nOrd rounded up to 32).  thx_step_compact_order_device: the same on
+ * device buffers (out: nOrd + 32 ints, nOut: 1 int), as the phases run it. */
+int thx_step_compact_order(const int* order, int nOrd, int cap, int* out, int* nOut);
+int thx_step_compact_order_device(const int* order, int nOrd, int* out, int* nOut,
+                                  thx_stream_t stream);
+
 /* ------------------------------------------------------------------ a2 ---
  * Per-image CTF over the pixel set: CTF(RFLOAT* dst, ...) (src/CTF.cpp:
  * 113-151), computed on device instead of on the host in allocPreCal
@@ -198,8 +212,13 @@ int thx_global_scan_dvp(const float* rotP, int nR, const float* traP, int nT,
  * 128 rotations fits in LDS it is staged there once and the 8 taps of every
  * sample are read from LDS, otherwise straight from `vol`.  The order only
  * changes the FP32 summation order over pixels, not which taps are summed.
+ * A phase that runs (or may be routed to) a kernel without LDS boxes visits
+ * the step-compacted order (thx_step_compact_order), built on the device from
+ * pxOrder; THX_STEP_COMPACTION=0 in the environment (read at every call)
+ * keeps the plain tile order -- same results, for A/B runs and tests.
  * workspace (required): >= thx_local_phase_workspace(nImg, nR, nT, nVisit)
- * bytes, nVisit = nOrd with pxOrder, nPxl without. */
+ * bytes, nVisit = nOrd with pxOrder, nPxl without (the compacted order and
+ * the per-image constants add 4 (nVisit + nImg) + 896 bytes to it). */
 size_t thx_local_phase_workspace(int nImg, int nR, int nT, int nVisit);
 int thx_local_phase(const float* vol, int volLayout, int vdim, int pf,
                     const double* quat,

@@ -121,6 +121,34 @@ extern "C" int thx_pixel_tile_order(const int* iCol, const int* iRow, int nPxl, 
     return THX_OK;
 }
 
+// The tile order without its all-padding steps, for the box-less local-phase
+// kernels: they gather every sample from L2, so a patch need not stay one
+// 16-entry group, and a step (4 aligned entries) of -1 only costs time.  Every
+// step that holds a pixel is kept as it is and in its place in the sequence;
+// the end is padded with -1 to a whole iteration of those kernels (32 entries).
+// k_step_compact (local.hip) is the same on the device.
+extern "C" int thx_step_compact_order(const int* order, int nOrd, int cap, int* out, int* nOut)
+{
+    constexpr int STEP = 4, ITER = 32;
+    THX_CHECK_ARG(nOut && nOrd >= 0 && nOrd % STEP == 0 && cap >= 0 && (order || nOrd == 0),
+                  "thx_step_compact_order: bad arguments (nOrd must be a multiple of 4)");
+    std::vector<int> o;
+    o.reserve(nOrd + ITER);
+    for (int s = 0; s < nOrd; s += STEP) {
+        bool any = false;
+        for (int k = 0; k < STEP; k++) any |= order[s + k] >= 0;
+        if (any) o.insert(o.end(), order + s, order + s + STEP);
+    }
+    o.resize((o.size() + ITER - 1) / ITER * ITER, -1);
+    *nOut = (int)o.size();
+    if (out) {
+        THX_CHECK_ARG((int)o.size() <= cap, "thx_step_compact_order: cap=%d < %d", cap,
+                      (int)o.size());
+        std::copy(o.begin(), o.end(), out);
+    }
+    return THX_OK;
+}
+
 // ---------------------------------------------------------------------- a2
 // One workgroup column per image, pixels across threads.  CTF(RFLOAT*, ...),
 // src/CTF.cpp:113-151 (ctf_at, common.h).

@@ -662,6 +662,101 @@ THX_DEV Pix load_pix(int p, const int* __restrict__ iCol, const int* __restrict_
     return x;
 }
 
+// Step plan of the box-less kernels.  They gather every sample from L2, so a
+// patch need not be one 16-entry group of the tile order, and the pair route
+// has no padding branch: a step of four -1 entries runs in full to add zero.
+// k_step_compact drops those steps (thx_step_compact_order, geom.hip, on the
+// device): `out` gets the kept steps in sequence, padded with -1 to a whole
+// 32-entry iteration, *nOut the length.  One workgroup; thread t owns a
+// contiguous run of steps, the runs' counts meet in LDS.
+constexpr int PLAN_A = 64;   // ints of a plan before its per-image constants ([0]: the length)
+__global__ void __launch_bounds__(256) k_step_compact(const int* __restrict__ order, int nOrd,
+                                                      int* __restrict__ out, int* __restrict__ nOut)
+{
+    __shared__ int sCnt[256];
+    const int tid = threadIdx.x;
+    const int nS = nOrd / 4, per = (nS + 255) / 256;
+    const int s0 = min(tid * per, nS), s1 = min(s0 + per, nS);
+    auto keep = [&](int s) {
+        return (order[4 * s] & order[4 * s + 1] & order[4 * s + 2] & order[4 * s + 3]) >= 0;
+    };
+    int n = 0;
+    for (int s = s0; s < s1; s++) n += keep(s);
+    sCnt[tid] = n;
+    __syncthreads();
+    int off = 0, tot = 0;
+    for (int j = 0; j < 256; j++) {
+        const int v = sCnt[j];
+        off += j < tid ? v : 0;
+        tot += v;
+    }
+    for (int s = s0; s < s1; s++)
+        if (keep(s)) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) out[4 * off + k] = order[4 * s + k];
+            off++;
+        }
+    const int len = (4 * tot + 31) / 32 * 32;     // <= nOrd + 28
+    for (int i = 4 * tot + tid; i < len; i += 256) out[i] = -1;
+    if (tid == 0) *nOut = len;
+}
+
+// A_l = sum_i s |d|^2 exactly as k_local_fused forms it over the tile order:
+// there staging thread 16 q sums the pixels at entries q, q + PKC, .. in turn,
+// wave w's four partial sums meet in wave_sum as (p[4w] + p[4w+2]) + (p[4w+1] +
+// p[4w+3]) -- every other lane adds +0 -- and the waves' sums are added in
+// turn from sRed.  Which thread a pixel falls to depends on its position in
+// the order, so over the compacted order the FP32 sum would round differently;
+// the box-less kernels take this one instead and a phase's outputs stay bit
+// for bit those of the tile order.  One wave per image, lane q = slot q, the
+// loads of IC_B iterations in flight together.
+constexpr int IC_WAVES = 4;      // images per workgroup
+constexpr int IC_B = 8;
+template <int PKC>
+__global__ void __launch_bounds__(64 * IC_WAVES) k_image_const(const int* __restrict__ order,
+                                                               int nOrd,
+                                                               const float2* __restrict__ dat,
+                                                               const float* __restrict__ sig,
+                                                               int nPxl, int nImg,
+                                                               const int* __restrict__ act,
+                                                               const int* __restrict__ nAct,
+                                                               float* __restrict__ aL)
+{
+    static_assert(PKC <= 32 && PKC % 4 == 0, "slots in the lower half of a wave");
+    const int lane = threadIdx.x & 63;
+    int l = blockIdx.x * IC_WAVES + (threadIdx.x >> 6);
+    if (l >= nImg) return;
+    if (act) {
+        if (l >= *nAct) return;
+        l = act[l];
+    }
+    const float2* D = dat + (size_t)l * nPxl;
+    const float* S = sig + (size_t)l * nPxl;
+    const int nIt = (nOrd + PKC - 1) / PKC;     // the kernel's iterations
+    float aConst = 0.f;
+    for (int it0 = 0; it0 < nIt; it0 += IC_B) {
+        int p[IC_B];
+        Pix x[IC_B];
+#pragma unroll
+        for (int j = 0; j < IC_B; j++)
+            p[j] = lane < PKC && it0 + j < nIt ? patch_pixel(order, nOrd, (it0 + j) * PKC + lane) : -1;
+#pragma unroll
+        for (int j = 0; j < IC_B; j++) {
+            const int q = max(p[j], 0);
+            x[j] = Pix{p[j], 0, 0, D[q], 0.f, S[q]};
+        }
+#pragma unroll
+        for (int j = 0; j < IC_B; j++)
+            if (x[j].p >= 0) aConst += x[j].s * (x[j].d.x * x[j].d.x + x[j].d.y * x[j].d.y);
+    }
+    aConst += __shfl_xor(aConst, 2, 64);
+    aConst += __shfl_xor(aConst, 1, 64);
+    float Al = 0.f;
+#pragma unroll
+    for (int k = 0; k < NWAVE; k++) Al += __shfl(aConst, 4 * k, 64);
+    if (lane == 0) aL[l] = Al;
+}
+
 // The items (4 consecutive voxels of a box row, 32 B) of a staged patch this
 // thread moves: item it = tid + j THREADS, LDS voxel dst[j].
 template <int LAYOUT, int NI = NIT, int CAP = BOX_CAP>
@@ -799,11 +894,16 @@ k_local_fused(const float2* __restrict__ vol,
                                                             float* __restrict__ wT = nullptr,
                                                             float* __restrict__ baseL = nullptr,
                                                             const int* __restrict__ route = nullptr,
-                                                            int ballR = 0)
+                                                            int ballR = 0,
+                                                            const int* __restrict__ plan = nullptr)
 {
     // routed phases launch the staged and the box-less kernel; one exits
     if (route && route_pick(route) != (LAYOUT == LAYOUT_YPAIR2 ? ROUTE_YPAIR
                                        : STAGE ? ROUTE_STAGED : ROUTE_NOBOX)) return;
+    // box-less kernels with a step plan: `order` is the step-compacted order
+    // (k_step_compact), its length is on the device, A_l in the plan
+    const bool planned = (coop_layout(LAYOUT) || LAYOUT == LAYOUT_YPAIR2 || !STAGE) && plan;
+    if (planned) nVisit = plan[0];
     int l = blockIdx.x;
     if (act) {
         if (l >= *nAct) return;
@@ -1194,6 +1294,7 @@ k_local_fused(const float2* __restrict__ vol,
     __syncthreads();
     float Al = 0.f;
     for (int k = 0; k < NWAVE; k++) Al += sRed[k];
+    if (planned) Al = reinterpret_cast<const float*>(plan + PLAN_A)[l];   // k_image_const
     if (!CS && wR) {
         // one workgroup holds the image's whole (r, t) table (nR <= 128, nT <=
         // 16): the per-image normalisation of k_local_weights
@@ -1554,9 +1655,53 @@ extern "C" int thx_volume_ypair(const float* vol, int vdim, float* ypair, thx_st
     return THX_OK;
 }
 
-extern "C" size_t thx_local_phase_workspace(int nImg, int nR, int nT, int nVisit)
+static size_t ws_without_plan(int nImg, int nR, int nT, int nVisit)
 {
     return dvp_bytes(nImg, nR, nT) + rec_bytes(nImg, nR, nVisit) + 256 + 768;
+}
+
+extern "C" size_t thx_local_phase_workspace(int nImg, int nR, int nT, int nVisit)
+{
+    // + the step plan of the box-less kernels: the compacted order (<= nVisit
+    // + 32 ints) and PLAN_A ints + one float per image, two carved buffers
+    return ws_without_plan(nImg, nR, nT, nVisit) +
+           sizeof(int) * ((size_t)nVisit + 32 + PLAN_A + nImg) + 512;
+}
+
+extern "C" int thx_step_compact_order_device(const int* order, int nOrd, int* out, int* nOut,
+                                             thx_stream_t stream)
+{
+    THX_CHECK_ARG(order && out && nOut && nOrd > 0 && nOrd % 4 == 0,
+                  "thx_step_compact_order_device: bad arguments (nOrd must be a multiple of 4)");
+    hipLaunchKernelGGL(k_step_compact, dim3(1), dim3(256), 0, thx::as_stream(stream), order, nOrd,
+                       out, nOut);
+    THX_LAUNCH_CHECK();
+    return THX_OK;
+}
+
+// THX_STEP_COMPACTION=0: the box-less kernels keep the plain tile order (A/B
+// runs and the bit-identity tests); read at every call, on the host
+static bool step_compaction_on()
+{
+    const char* e = std::getenv("THX_STEP_COMPACTION");
+    return !(e && e[0] == '0' && e[1] == '\0');
+}
+
+// The step plan of a phase: cOrd (nOrd + 32 ints) gets the compacted order,
+// plan (PLAN_A + nImg ints) its length and, per image (of the active list,
+// or all), A_l as the kernel with nD's iteration size sums it over pxOrder.
+static int step_plan_launch(const int* pxOrder, int nOrd, const float* dat, const float* sigRcp,
+                            int nPxl, int nImg, int nD, const int* act, const int* nAct, int* cOrd,
+                            int* plan, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_step_compact, dim3(1), dim3(256), 0, s, pxOrder, nOrd, cOrd, plan);
+    THX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(nD ? k_image_const<KC> : k_image_const<2 * KC>,
+                       dim3(thx::cdiv(nImg, IC_WAVES)), dim3(64 * IC_WAVES), 0, s, pxOrder, nOrd,
+                       reinterpret_cast<const float2*>(dat), sigRcp, nPxl, nImg, act, nAct,
+                       reinterpret_cast<float*>(plan + PLAN_A));
+    THX_LAUNCH_CHECK();
+    return THX_OK;
 }
 
 // nD = 0: the phase without CTF search; nD >= 1: CTF search over nD defocus
@@ -1571,7 +1716,8 @@ static int local_phase_impl(const thx_local_sel* sel, hipEvent_t evBeg, hipEvent
                             size_t wsBytes, thx_stream_t stream, int nD = 0,
                             const double* pD = nullptr, float* wD = nullptr,
                             const float* ypair = nullptr, int* routeOut = nullptr,
-                            const int* const* routeSample = nullptr, int ypairR = 0)
+                            const int* const* routeSample = nullptr, int ypairR = 0,
+                            const int* const* stepPlan = nullptr)
 {
     THX_CHECK_ARG(nR > 0 && nT > 0 && nPxl > 0 && nImg >= 0 && vdim > 0 && pf > 0 && nD >= 0,
                   "thx_local_phase: bad sizes");
@@ -1594,20 +1740,39 @@ static int local_phase_impl(const thx_local_sel* sel, hipEvent_t evBeg, hipEvent
     THX_CHECK_ARG(!ypair || (volLayout == LAYOUT_FT && pxOrder && !nD),
                   "thx_local_phase_routed: a y-pair copy goes with the half-complex layout and pxOrder");
     const int nVisit = pxOrder ? nOrd : nPxl;
-    THX_CHECK_ARG(workspace && wsBytes >= thx_local_phase_workspace(nImg, nR, nCol, nVisit),
-                  "thx_local_phase: workspace too small");
-    thx::Carver ws(workspace, wsBytes);
-    float* d = dvp ? dvp : ws.take<float>((size_t)nImg * nR * nCol);
-    int* rec = ws.take<int>(rec_bytes(nImg, nR, nVisit) / sizeof(int));
-    int* route = ws.take<int>(64);
-    hipStream_t s = thx::as_stream(stream);
     // big LDS boxes for large full-resolution pixel sets: the ring's outer
     // radius in projectee voxels, pf sqrt(2 nPxl / pi), past BIGBOX_MIN_R
     const bool big = pf * std::sqrt(2.0 * nPxl / M_PI) >= BIGBOX_MIN_R;
     // the staged / box-less (or y-pair) route of a half-complex phase, chosen
     // on the device from a sample of the patch records (route_pick)
     const bool routed = volLayout == LAYOUT_FT && !nD && !big;
+    // a phase that runs, or may be routed to, a box-less kernel takes a step
+    // plan: the caller's (stepPlan = {order, plan} of thx::step_plan_build: the
+    // driver builds one per call, for all its phases) or one built here in the
+    // workspace (two small launches, no host round trip).  The staged kernel,
+    // the records and the route's sample keep pxOrder.
+    const bool nobox = routed || coop_layout(volLayout) || volLayout == LAYOUT_YPAIR2;
+    const bool compact = nobox && pxOrder && step_compaction_on();
+    const bool ownPlan = compact && !stepPlan;
+    THX_CHECK_ARG(workspace && wsBytes >= (ownPlan ? thx_local_phase_workspace(nImg, nR, nCol, nVisit)
+                                                   : ws_without_plan(nImg, nR, nCol, nVisit)),
+                  "thx_local_phase: workspace too small");
+    thx::Carver ws(workspace, wsBytes);
+    float* d = dvp ? dvp : ws.take<float>((size_t)nImg * nR * nCol);
+    int* rec = ws.take<int>(rec_bytes(nImg, nR, nVisit) / sizeof(int));
+    int* route = ws.take<int>(64);
+    hipStream_t s = thx::as_stream(stream);
     const unsigned nRT = thx::cdiv(nR, RT);
+    const int* cOrd = compact && stepPlan ? stepPlan[0] : nullptr;
+    const int* plan = compact && stepPlan ? stepPlan[1] : nullptr;
+    if (ownPlan) {
+        int* o = ws.take<int>((size_t)nVisit + 32);
+        int* pl = ws.take<int>((size_t)PLAN_A + nImg);
+        THX_RET(step_plan_launch(pxOrder, nOrd, dat, sigRcp, nPxl, nImg, nD, act, nAct, o, pl, s));
+        cOrd = o;
+        plan = pl;
+    }
+    const int* nbOrder = plan ? cOrd : pxOrder;     // the box-less kernels' order
     if (routed) {
         THX_HIP(hipMemsetAsync(route, 0, 2 * sizeof(int), s));
         THX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(route + 2), ypair ? 1 : 0, 1, s));
@@ -1653,9 +1818,10 @@ static int local_phase_impl(const thx_local_sel* sel, hipEvent_t evBeg, hipEvent
         grid.z = thx::cdiv(nCol, TT * nct);
         hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s, reinterpret_cast<const float2*>(vol),
                            vdim, pf, quat, nR, trans, nCol, reinterpret_cast<const float2*>(dat),
-                           ctf, sigRcp, iCol, iRow, pxOrder, nVisit, nPxl, idim, rec, d, act, nAct,
-                           cls, vs, nD, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, 0);
+                           ctf, sigRcp, iCol, iRow, coop_layout(volLayout) ? nbOrder : pxOrder, nVisit,
+                           nPxl, idim, rec, d, act, nAct, cls, vs, nD, nullptr, nullptr, nullptr,
+                           nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                           coop_layout(volLayout) ? plan : nullptr);
         THX_LAUNCH_CHECK();
         if (evEnd) THX_HIP(hipEventRecord(evEnd, s));
         hipLaunchKernelGGL(k_local_weights_d, dim3(nImg), dim3(256), 0, s, d, nR, nT, nD, pC, pR,
@@ -1672,31 +1838,33 @@ static int local_phase_impl(const thx_local_sel* sel, hipEvent_t evBeg, hipEvent
     // the normalisation runs in the kernel's epilogue and dvp is only written
     // when the caller asks for it
     const bool fuse = grid.y == 1 && grid.z == 1;
-    auto launch = [&](auto k, const int* rt) {
+    // boxless: the kernel has no LDS boxes and takes the step plan
+    auto launch = [&](auto k, const int* rt, bool boxless) {
         hipLaunchKernelGGL(k, grid, dim3(THREADS), 0, s, reinterpret_cast<const float2*>(vol), vdim,
                            pf, quat, nR, trans, nT, reinterpret_cast<const float2*>(dat), ctf, sigRcp,
-                           iCol, iRow, pxOrder, nVisit, nPxl, idim, rec, fuse ? dvp : d, act, nAct,
-                           cls, vs, 1, pC, pR, pT, fuse ? wC : nullptr, fuse ? wR : nullptr,
-                           fuse ? wT : nullptr, fuse ? baseL : nullptr, rt, 0);
+                           iCol, iRow, boxless ? nbOrder : pxOrder, nVisit, nPxl, idim, rec,
+                           fuse ? dvp : d, act, nAct, cls, vs, 1, pC, pR, pT, fuse ? wC : nullptr,
+                           fuse ? wR : nullptr, fuse ? wT : nullptr, fuse ? baseL : nullptr, rt, 0,
+                           boxless ? plan : nullptr);
     };
     if (routed) {
         // two launches, the staged kernel and (with a y-pair copy) the pair-form
         // y-pair kernel or (without) the box-less half-complex one; the kernel
         // the route did not pick exits at entry
-        launch(k_local_fused<LAYOUT_FT, false, 1, false, true>, route);
+        launch(k_local_fused<LAYOUT_FT, false, 1, false, true>, route, false);
         if (ypair) {
             hipLaunchKernelGGL(k_local_fused<LAYOUT_YPAIR2>, grid, dim3(THREADS), 0, s,
                                reinterpret_cast<const float2*>(ypair), vdim, pf, quat, nR, trans, nT,
-                               reinterpret_cast<const float2*>(dat), ctf, sigRcp, iCol, iRow, pxOrder,
+                               reinterpret_cast<const float2*>(dat), ctf, sigRcp, iCol, iRow, nbOrder,
                                nVisit, nPxl, idim, rec, fuse ? dvp : d, act, nAct, cls,
                                cls ? (ypairR > 0 ? 2L * (long)thx::ypair_ball_elems(ypairR) : 2 * vs) : 0L, 1,
                                pC, pR, pT, fuse ? wC : nullptr, fuse ? wR : nullptr,
-                               fuse ? wT : nullptr, fuse ? baseL : nullptr, route, ypairR);
+                               fuse ? wT : nullptr, fuse ? baseL : nullptr, route, ypairR, plan);
         } else {
-            launch(k_local_fused<LAYOUT_FT, false, 1, false, false>, route);
+            launch(k_local_fused<LAYOUT_FT, false, 1, false, false>, route, true);
         }
     } else {
-        launch(kern, nullptr);
+        launch(kern, nullptr, nobox);
     }
     THX_LAUNCH_CHECK();
     if (evEnd) THX_HIP(hipEventRecord(evEnd, s));
@@ -1858,12 +2026,32 @@ int local_phase_timed(const thx_local_sel* sel, hipEvent_t evBeg, hipEvent_t evE
                       int idim, int nImg, float* wC, float* wR, float* wT, float* baseL,
                       void* workspace, size_t wsBytes, thx_stream_t stream, int nD,
                       const double* pD, float* wD, const float* ypair, int* routeOut,
-                      const int* const* routeSample, int ypairR)
+                      const int* const* routeSample, int ypairR, const int* const* stepPlan)
 {
     return local_phase_impl(sel, evBeg, evEnd, vol, volLayout, vdim, pf, quat, nR, trans, nT, pC,
                             pR, pT, dat, ctf, sigRcp, iCol, iRow, pxOrder, nOrd, nPxl, idim, nImg,
                             wC, wR, wT, baseL, nullptr, workspace, wsBytes, stream, nD, pD, wD,
-                            ypair, routeOut, routeSample, ypairR);
+                            ypair, routeOut, routeSample, ypairR, stepPlan);
+}
+
+// The driver's side of the step plan: a phase given one needs the workspace
+// without the plan's share, and the plan (order: nOrd + 32 ints, plan:
+// step_plan_ints(nImg) ints) serves every phase of a call -- the order, the
+// images' data and sigma do not change between them.  False (nothing
+// launched) with THX_STEP_COMPACTION=0.
+size_t local_phase_workspace_planned(int nImg, int nR, int nT, int nVisit)
+{
+    return ws_without_plan(nImg, nR, nT, nVisit);
+}
+size_t step_plan_ints(int nImg) { return (size_t)PLAN_A + nImg; }
+bool step_plan_build(const int* pxOrder, int nOrd, const float* dat, const float* sigRcp, int nPxl,
+                     int nImg, int nD, int* cOrd, int* plan, hipStream_t s, int* status)
+{
+    *status = THX_OK;
+    if (!pxOrder || nOrd <= 0 || nOrd % KC || nImg <= 0 || !step_compaction_on()) return false;
+    *status = step_plan_launch(pxOrder, nOrd, dat, sigRcp, nPxl, nImg, nD, nullptr, nullptr, cOrd,
+                               plan, s);
+    return *status == THX_OK;
 }
 
 // whether local_phase_impl routes a phase on the device (half-complex layout,

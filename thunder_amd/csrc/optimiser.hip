@@ -58,7 +58,12 @@ int local_phase_timed(const thx_local_sel* sel, hipEvent_t evBeg, hipEvent_t evE
                       void* workspace, size_t wsBytes, thx_stream_t stream, int nD = 0,
                       const double* pD = nullptr, float* wD = nullptr,
                       const float* ypair = nullptr, int* routeOut = nullptr,
-                      const int* const* routeSample = nullptr, int ypairR = 0);
+                      const int* const* routeSample = nullptr, int ypairR = 0,
+                      const int* const* stepPlan = nullptr);
+size_t local_phase_workspace_planned(int nImg, int nR, int nT, int nVisit);
+size_t step_plan_ints(int nImg);
+bool step_plan_build(const int* pxOrder, int nOrd, const float* dat, const float* sigRcp, int nPxl,
+                     int nImg, int nD, int* cOrd, int* plan, hipStream_t s, int* status);
 size_t ypair_ball_elems(int R);
 int volume_ypair_ball(const float* vol, int vdim, int R, float* ypair, hipStream_t s);
 bool phase_routed(int volLayout, int pf, int nPxl, int nD);
@@ -1753,6 +1758,7 @@ struct Plan {
     double* bestR; double* bestT;                        // convergence: smallest variR / variT
     void* localWs; size_t localWsBytes;
     float* ypair;                        // y-pair projectees (thx_volume_ypair), per class
+    int* stepOrd; int* stepPlan;         // the phases' step plan (thx::step_plan_build)
     // CTF search: defocus precalculation, per-phase CTF table, D statistics
     float* freq; float* dfo; float* K1; float* K2; float* ctfD; float* wD;
     double* sdD; double* bestD; double* tmpD; int* topD;
@@ -1820,8 +1826,8 @@ Plan plan(void* base, const thx_expect_cfg& c, int nImg, int nPxl, int nVisit, i
     p.bestR = k.take<double>(nImg);
     p.bestT = k.take<double>(nImg);
     p.localWsBytes = twoD ? thx_local_phase2d_d_workspace(nImg, c.mLR, c.mLT, mLD)
-                          : thx_local_phase_workspace(nImg, c.mLR, c.mLT * (mLD > 0 ? mLD : 1),
-                                                      nVisit);
+                          : thx::local_phase_workspace_planned(nImg, c.mLR,
+                                                               c.mLT * (mLD > 0 ? mLD : 1), nVisit);
     p.localWs = k.take<char>(p.localWsBytes);
     const size_t nd = mLD > 0 ? (size_t)mLD : 0, on = mLD > 0 ? 1 : 0;
     p.freq = k.take<float>(on * nPxl);
@@ -1852,6 +1858,11 @@ Plan plan(void* base, const thx_expect_cfg& c, int nImg, int nPxl, int nVisit, i
         }
     }
     p.ypair = yp ? k.take<float>((size_t)4 * (c.vdim / 2 + 1) * c.vdim * c.vdim * nK) : nullptr;
+    // the step plan of the box-less phase kernels, one per call (after the
+    // y-pair copy: the buffers before it stay where they were; 4 (nVisit +
+    // nImg) + 384 bytes, + up to 512 of alignment)
+    p.stepOrd = k.take<int>(!twoD ? (size_t)nVisit + 32 : 0);
+    p.stepPlan = k.take<int>(!twoD ? thx::step_plan_ints(nImg) : 0);
     p.bytes = k.off + 256;
     return p;
 }
@@ -2395,6 +2406,16 @@ static int expectation_impl(const thx_expect_cfg* cfg, const thx_ctf_search_cfg*
         sel.active = p.act;
         sel.nActive = p.nAct;
     }
+    // the step plan of the box-less phase kernels: the tile order without its
+    // all-padding steps and the images' A_l, the same for every phase
+    const int* stepPlan[2] = {p.stepOrd, p.stepPlan};
+    bool planned = false;
+    if (!twoD && nPh > 0) {
+        int st = THX_OK;
+        planned = thx::step_plan_build(pxOrder, nOrd, dat, sigRcp, nPxl, nImg, mLD, p.stepOrd,
+                                       p.stepPlan, s, &st);
+        THX_RET(st);
+    }
     // the particle clouds ping-pong between the caller's buffers and
     // tmpQ / tmpT: a phase reads the current pair and the resampling gathers
     // into the other (the pre-resample cloud stays readable for calVari and
@@ -2464,7 +2485,7 @@ static int expectation_impl(const thx_expect_cfg* cfg, const thx_ctf_search_cfg*
                                        nPxl, c.idim, nImg, p.wC, p.wR, p.wT, p.base, p.localWs,
                                        p.localWsBytes, stream, mLD, cs ? cs->pD : nullptr, p.wD,
                                        p.ypair, pi < c.nPhaseRoute ? c.phaseRoute + pi : nullptr,
-                                       routeSample, ypairR));
+                                       routeSample, ypairR, planned ? stepPlan : nullptr));
         hipLaunchKernelGGL(k_pf_peak, dim3(gImg), dim3(256), 0, s, nImg, c.mLR, p.wR, c.mLR,
                            p.peakR, 0, nullptr, 0, done, rankDiv);
         THX_LAUNCH_CHECK();

@@ -105,6 +105,31 @@ def tile_order(iCol, iRow):
     return order
 
 
+def step_compact_order(order):
+    """thx_step_compact_order: the tile order without its all-padding steps (4
+    aligned entries of -1), padded with -1 to a multiple of 32 -- the order the
+    box-less local-phase kernels visit."""
+    order = np.ascontiguousarray(order, np.int32)
+    out = np.zeros(len(order) + 32, np.int32)
+    n = ctypes.c_int(0)
+    vp = ctypes.c_void_p
+    check(lib().thx_step_compact_order(order.ctypes.data_as(vp), len(order), len(out),
+                                       out.ctypes.data_as(vp), ctypes.byref(n)),
+          "thx_step_compact_order")
+    return out[:n.value].copy()
+
+
+def step_compact_order_device(order):
+    """The same on the device (int32 tensor in, int32 tensor out), as the phases run it."""
+    _req(order, torch.int32, (order.numel(),), "order")
+    out = torch.empty(order.numel() + 32, dtype=torch.int32, device=order.device)
+    n = torch.zeros(1, dtype=torch.int32, device=order.device)
+    check(lib().thx_step_compact_order_device(_ptr(order), order.numel(), _ptr(out), _ptr(n),
+                                              _stream(order.device)),
+          "thx_step_compact_order_device")
+    return out[:int(n.item())].clone()
+
+
 # ------------------------------------------------------------------- a2
 def ctf(attr, px):
     """attr: [nImg, 8] float32 {pixelSize, voltage, dU, dV, theta, Cs, ampC, phaseShift}."""
