@@ -40,6 +40,13 @@ void set_error(const char* fmt, ...);
 
 #define THX_LAUNCH_CHECK() THX_HIP(hipGetLastError())
 
+// a kernel launch (hipLaunchKernelGGL's arguments) with its launch check
+#define THX_LAUNCH(...)                  \
+    do {                                 \
+        hipLaunchKernelGGL(__VA_ARGS__); \
+        THX_LAUNCH_CHECK();              \
+    } while (0)
+
 // propagate a THX_* status
 #define THX_RET(call)                  \
     do {                               \

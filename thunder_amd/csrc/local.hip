@@ -45,7 +45,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "common.h"
+#include "internal.h"
 #include "patch.h"
 
 namespace {
@@ -198,7 +198,7 @@ THX_DEV unsigned ypair_elem(unsigned z, unsigned y, unsigned x, unsigned vdim, u
 // In the compact ball slices z and z + 1 (z + R even) are interleaved element
 // by element, so for such z0 a sample's four 16-B elements (x0, x0 + 1 of
 // both slices) are one contiguous 64-B piece
-// ballR > 0: the copy is the compact ball of thx::volume_ypair_ball --
+// ballR > 0: the copy is the compact ball of thx_volume_ypair_ball --
 // elements (x, y, z), 0 <= x < ballR + 2, -ballR <= y, z < ballR + 2, no
 // wrap (every tap of the pixel ring lies inside)
 THX_DEV unsigned ypair_ball_elem(int z, int y, int x, int ballR)
@@ -1604,9 +1604,8 @@ int launch_local_weights(const float* dvp, int nR, int nT, const double* pC, con
                          const double* pT, float* wC, float* wR, float* wT, float* baseL, int nImg,
                          hipStream_t s, const int* act, const int* nAct)
 {
-    hipLaunchKernelGGL(k_local_weights, dim3(nImg), dim3(256), 0, s, dvp, nR, nT, pC, pR, pT, wC,
-                       wR, wT, baseL, act, nAct);
-    THX_LAUNCH_CHECK();
+    THX_LAUNCH(k_local_weights, dim3(nImg), dim3(256), 0, s, dvp, nR, nT, pC, pR, pT, wC,
+               wR, wT, baseL, act, nAct);
     return THX_OK;
 }
 
@@ -1615,9 +1614,8 @@ int launch_local_weights_d(const float* dvp, int nR, int nT, int nD, const doubl
                            float* wR, float* wT, float* wD, float* baseL, int nImg, hipStream_t s,
                            const int* act, const int* nAct)
 {
-    hipLaunchKernelGGL(k_local_weights_d, dim3(nImg), dim3(256), 0, s, dvp, nR, nT, nD, pC, pR,
-                       pT, pD, wC, wR, wT, wD, baseL, act, nAct);
-    THX_LAUNCH_CHECK();
+    THX_LAUNCH(k_local_weights_d, dim3(nImg), dim3(256), 0, s, dvp, nR, nT, nD, pC, pR,
+               pT, pD, wC, wR, wT, wD, baseL, act, nAct);
     return THX_OK;
 }
 
@@ -1625,13 +1623,10 @@ int launch_patch_boxes(const double* quat, int nR, const int* iCol, const int* i
                        const int* order, int nVisit, int pf, int vdim, int nImg, int* rec,
                        hipStream_t s)
 {
-    hipLaunchKernelGGL(k_patch_boxes, dim3((unsigned)nImg * cdiv(nR, RT)), dim3(64 * PB_WAVES), 0,
-                       s, quat, nR, iCol, iRow, order, nVisit, pf, vdim, rec, nullptr, nullptr);
-    THX_LAUNCH_CHECK();
+    THX_LAUNCH(k_patch_boxes, dim3((unsigned)nImg * cdiv(nR, RT)), dim3(64 * PB_WAVES), 0,
+               s, quat, nR, iCol, iRow, order, nVisit, pf, vdim, rec, nullptr, nullptr);
     return THX_OK;
 }
-
-size_t ypair_ball_elems(int R);
 
 }  // namespace thx
 
@@ -1655,7 +1650,7 @@ extern "C" int thx_volume_ypair(const float* vol, int vdim, float* ypair, thx_st
     return THX_OK;
 }
 
-static size_t ws_without_plan(int nImg, int nR, int nT, int nVisit)
+size_t thx::local_phase_workspace_planned(int nImg, int nR, int nT, int nVisit)
 {
     return dvp_bytes(nImg, nR, nT) + rec_bytes(nImg, nR, nVisit) + 256 + 768;
 }
@@ -1664,7 +1659,7 @@ extern "C" size_t thx_local_phase_workspace(int nImg, int nR, int nT, int nVisit
 {
     // + the step plan of the box-less kernels: the compacted order (<= nVisit
     // + 32 ints) and PLAN_A ints + one float per image, two carved buffers
-    return ws_without_plan(nImg, nR, nT, nVisit) +
+    return thx::local_phase_workspace_planned(nImg, nR, nT, nVisit) +
            sizeof(int) * ((size_t)nVisit + 32 + PLAN_A + nImg) + 512;
 }
 
@@ -1706,18 +1701,18 @@ static int step_plan_launch(const int* pxOrder, int nOrd, const float* dat, cons
 
 // nD = 0: the phase without CTF search; nD >= 1: CTF search over nD defocus
 // samples (ctf = ctfD[nImg][nD][nPxl], priors pD[nImg][nD], marginal wD).
-static int local_phase_impl(const thx_local_sel* sel, hipEvent_t evBeg, hipEvent_t evEnd,
-                            const float* vol, int volLayout, int vdim,
-                            int pf, const double* quat, int nR, const double* trans, int nT,
-                            const double* pC, const double* pR, const double* pT, const float* dat,
-                            const float* ctf, const float* sigRcp, const int* iCol, const int* iRow,
-                            const int* pxOrder, int nOrd, int nPxl, int idim, int nImg, float* wC,
-                            float* wR, float* wT, float* baseL, float* dvp, void* workspace,
-                            size_t wsBytes, thx_stream_t stream, int nD = 0,
-                            const double* pD = nullptr, float* wD = nullptr,
-                            const float* ypair = nullptr, int* routeOut = nullptr,
-                            const int* const* routeSample = nullptr, int ypairR = 0,
-                            const int* const* stepPlan = nullptr)
+// Behind the C-ABI entry points below and, with the phase kernel's event pair,
+// the expectation driver.
+int thx::local_phase_impl(const thx_local_sel* sel, hipEvent_t evBeg, hipEvent_t evEnd,
+                          const float* vol, int volLayout, int vdim,
+                          int pf, const double* quat, int nR, const double* trans, int nT,
+                          const double* pC, const double* pR, const double* pT, const float* dat,
+                          const float* ctf, const float* sigRcp, const int* iCol, const int* iRow,
+                          const int* pxOrder, int nOrd, int nPxl, int idim, int nImg, float* wC,
+                          float* wR, float* wT, float* baseL, float* dvp, void* workspace,
+                          size_t wsBytes, thx_stream_t stream, int nD, const double* pD, float* wD,
+                          const float* ypair, int* routeOut, const int* const* routeSample,
+                          int ypairR, const int* const* stepPlan)
 {
     THX_CHECK_ARG(nR > 0 && nT > 0 && nPxl > 0 && nImg >= 0 && vdim > 0 && pf > 0 && nD >= 0,
                   "thx_local_phase: bad sizes");
@@ -1755,7 +1750,7 @@ static int local_phase_impl(const thx_local_sel* sel, hipEvent_t evBeg, hipEvent
     const bool compact = nobox && pxOrder && step_compaction_on();
     const bool ownPlan = compact && !stepPlan;
     THX_CHECK_ARG(workspace && wsBytes >= (ownPlan ? thx_local_phase_workspace(nImg, nR, nCol, nVisit)
-                                                   : ws_without_plan(nImg, nR, nCol, nVisit)),
+                                                   : local_phase_workspace_planned(nImg, nR, nCol, nVisit)),
                   "thx_local_phase: workspace too small");
     thx::Carver ws(workspace, wsBytes);
     float* d = dvp ? dvp : ws.take<float>((size_t)nImg * nR * nCol);
@@ -1824,10 +1819,8 @@ static int local_phase_impl(const thx_local_sel* sel, hipEvent_t evBeg, hipEvent
                            coop_layout(volLayout) ? plan : nullptr);
         THX_LAUNCH_CHECK();
         if (evEnd) THX_HIP(hipEventRecord(evEnd, s));
-        hipLaunchKernelGGL(k_local_weights_d, dim3(nImg), dim3(256), 0, s, d, nR, nT, nD, pC, pR,
-                           pT, pD, wC, wR, wT, wD, baseL, act, nAct);
-        THX_LAUNCH_CHECK();
-        return THX_OK;
+        return launch_local_weights_d(d, nR, nT, nD, pC, pR, pT, pD, wC, wR, wT, wD, baseL, nImg, s,
+                                      act, nAct);
     }
     auto kern =
         volLayout == LAYOUT_YPAIR2 ? k_local_fused<LAYOUT_YPAIR2>
@@ -1857,7 +1850,7 @@ static int local_phase_impl(const thx_local_sel* sel, hipEvent_t evBeg, hipEvent
                                reinterpret_cast<const float2*>(ypair), vdim, pf, quat, nR, trans, nT,
                                reinterpret_cast<const float2*>(dat), ctf, sigRcp, iCol, iRow, nbOrder,
                                nVisit, nPxl, idim, rec, fuse ? dvp : d, act, nAct, cls,
-                               cls ? (ypairR > 0 ? 2L * (long)thx::ypair_ball_elems(ypairR) : 2 * vs) : 0L, 1,
+                               cls ? (ypairR > 0 ? 2L * (long)thx_ypair_ball_elems(ypairR) : 2 * vs) : 0L, 1,
                                pC, pR, pT, fuse ? wC : nullptr, fuse ? wR : nullptr,
                                fuse ? wT : nullptr, fuse ? baseL : nullptr, route, ypairR, plan);
         } else {
@@ -1868,13 +1861,10 @@ static int local_phase_impl(const thx_local_sel* sel, hipEvent_t evBeg, hipEvent
     }
     THX_LAUNCH_CHECK();
     if (evEnd) THX_HIP(hipEventRecord(evEnd, s));
-    if (!fuse) {
-        hipLaunchKernelGGL(k_local_weights, dim3(nImg), dim3(256), 0, s, d, nR, nT, pC, pR, pT, wC,
-                           wR, wT, baseL, act, nAct);
-        THX_LAUNCH_CHECK();
-    }
-    return THX_OK;
+    if (fuse) return THX_OK;
+    return launch_local_weights(d, nR, nT, pC, pR, pT, wC, wR, wT, baseL, nImg, s, act, nAct);
 }
+using thx::local_phase_impl;
 
 extern "C" int thx_local_phase(const float* vol, int volLayout, int vdim, int pf,
                                const double* quat, int nR, const double* trans,
@@ -2005,44 +1995,11 @@ extern "C" int thx_local_phase_routed_ball(const thx_local_sel* sel, const float
 }
 
 namespace thx {
-// float4 elements of the compact y-pair ball of radius R
-size_t ypair_ball_elems(int R) { return (size_t)(R + 2) * (2 * R + 2) * (2 * R + 2); }
-
-int volume_ypair_ball(const float* vol, int vdim, int R, float* ypair, hipStream_t s)
-{
-    THX_CHECK_ARG(vol && ypair && vdim > 0 && vdim % 2 == 0 && R > 0 && R + 2 <= vdim / 2 + 1,
-                  "volume_ypair_ball: bad arguments");
-    hipLaunchKernelGGL(k_volume_ypair_ball, dim3(2048), dim3(256), 0, s,
-                       reinterpret_cast<const float2*>(vol), vdim, R, reinterpret_cast<float4*>(ypair));
-    THX_LAUNCH_CHECK();
-    return THX_OK;
-}
-
-int local_phase_timed(const thx_local_sel* sel, hipEvent_t evBeg, hipEvent_t evEnd,
-                      const float* vol, int volLayout, int vdim, int pf, const double* quat, int nR,
-                      const double* trans, int nT, const double* pC, const double* pR,
-                      const double* pT, const float* dat, const float* ctf, const float* sigRcp,
-                      const int* iCol, const int* iRow, const int* pxOrder, int nOrd, int nPxl,
-                      int idim, int nImg, float* wC, float* wR, float* wT, float* baseL,
-                      void* workspace, size_t wsBytes, thx_stream_t stream, int nD,
-                      const double* pD, float* wD, const float* ypair, int* routeOut,
-                      const int* const* routeSample, int ypairR, const int* const* stepPlan)
-{
-    return local_phase_impl(sel, evBeg, evEnd, vol, volLayout, vdim, pf, quat, nR, trans, nT, pC,
-                            pR, pT, dat, ctf, sigRcp, iCol, iRow, pxOrder, nOrd, nPxl, idim, nImg,
-                            wC, wR, wT, baseL, nullptr, workspace, wsBytes, stream, nD, pD, wD,
-                            ypair, routeOut, routeSample, ypairR, stepPlan);
-}
-
 // The driver's side of the step plan: a phase given one needs the workspace
 // without the plan's share, and the plan (order: nOrd + 32 ints, plan:
 // step_plan_ints(nImg) ints) serves every phase of a call -- the order, the
 // images' data and sigma do not change between them.  False (nothing
 // launched) with THX_STEP_COMPACTION=0.
-size_t local_phase_workspace_planned(int nImg, int nR, int nT, int nVisit)
-{
-    return ws_without_plan(nImg, nR, nT, nVisit);
-}
 size_t step_plan_ints(int nImg) { return (size_t)PLAN_A + nImg; }
 bool step_plan_build(const int* pxOrder, int nOrd, const float* dat, const float* sigRcp, int nPxl,
                      int nImg, int nD, int* cOrd, int* plan, hipStream_t s, int* status)

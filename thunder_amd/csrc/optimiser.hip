@@ -28,6 +28,7 @@
 // k_pf_resample).  Not replicated: the generator -- sampling is counter-based
 // (Philox4x32-10), so a run is reproducible for a given seed, where the
 // reference draws from an urandom-seeded GSL mt19937.
+#include <algorithm>
 #include <cmath>
 #include <map>
 #include <mutex>
@@ -35,45 +36,8 @@
 #include <string>
 #include <utility>
 
-#include "common.h"
+#include "internal.h"
 #include "symmetry.h"
-
-
-namespace thx {
-int project2d_launch(const float* vol, int vdim, int pf, const double* rot, int rotStride, int nR,
-                     const int* iCol, const int* iRow, int nPxl, float* rotP, hipStream_t s);
-int local_phase2d_launch(const float* vol, int vdim, int pf, const int* cls, const double* rot,
-                         int rotStride, int nR, const double* trans, int nT, const double* pC,
-                         const double* pR, const double* pT, const float* dat, const float* ctf,
-                         const float* sigRcp, const int* iCol, const int* iRow, int nPxl, int idim,
-                         int nImg, float* wC, float* wR, float* wT, float* baseL, float* dvp,
-                         const int* done, hipStream_t s, int nD = 0, const double* pD = nullptr,
-                         float* wD = nullptr, const int* act = nullptr, const int* nAct = nullptr);
-int local_phase_timed(const thx_local_sel* sel, hipEvent_t evBeg, hipEvent_t evEnd,
-                      const float* vol, int volLayout, int vdim, int pf, const double* quat, int nR,
-                      const double* trans, int nT, const double* pC, const double* pR,
-                      const double* pT, const float* dat, const float* ctf, const float* sigRcp,
-                      const int* iCol, const int* iRow, const int* pxOrder, int nOrd, int nPxl,
-                      int idim, int nImg, float* wC, float* wR, float* wT, float* baseL,
-                      void* workspace, size_t wsBytes, thx_stream_t stream, int nD = 0,
-                      const double* pD = nullptr, float* wD = nullptr,
-                      const float* ypair = nullptr, int* routeOut = nullptr,
-                      const int* const* routeSample = nullptr, int ypairR = 0,
-                      const int* const* stepPlan = nullptr);
-size_t local_phase_workspace_planned(int nImg, int nR, int nT, int nVisit);
-size_t step_plan_ints(int nImg);
-bool step_plan_build(const int* pxOrder, int nOrd, const float* dat, const float* sigRcp, int nPxl,
-                     int nImg, int nD, int* cOrd, int* plan, hipStream_t s, int* status);
-size_t ypair_ball_elems(int R);
-int volume_ypair_ball(const float* vol, int vdim, int R, float* ypair, hipStream_t s);
-bool phase_routed(int volLayout, int pf, int nPxl, int nD);
-int pf_symmetrise_launch(int nImg, int mR, double* quat, int anchorMode, const double* anchor,
-                         const double* symQ, int nSym, uint64_t seed, uint32_t stream,
-                         const int* done, hipStream_t s);
-size_t view_order_tmp_bytes(int nImg);
-int view_order(int nImg, int mLR, const double* quat, unsigned* keys, unsigned* keysOut, int* idx,
-               int* ord, void* tmp, size_t tmpBytes, hipStream_t s);
-}
 
 // max iCol^2 + iRow^2 over the pixel set (one workgroup)
 __global__ void __launch_bounds__(256) k_max_r2(const int* __restrict__ iCol,
@@ -98,7 +62,6 @@ static bool env_on(const char* name)
     const char* e = std::getenv(name);
     return !(e && e[0] == '0');
 }
-static bool view_order_on() { return env_on("THX_VIEW_ORDER"); }
 
 namespace {
 
@@ -1101,7 +1064,7 @@ __global__ void __launch_bounds__(256) k_pf_resample(int nImg, int nIn, int nOut
 
 using ResampleKernel = decltype(&k_pf_resample<4>);
 // supports up to 256 entries sort in the resampling kernel's registers; the
-// reseed's 2000 go through k_pf_shuffle_perm first (resample_launch)
+// reseed's 2000 go through k_pf_shuffle_perm first (both from resample_launch)
 ResampleKernel resample_kernel(int nIn, bool shuffle)
 {
     return shuffle && nIn > 256 && nIn <= RESAMPLE_KMAX ? &k_pf_resample<4, true> : &k_pf_resample<4>;
@@ -1116,6 +1079,34 @@ void shuffle_perm_launch(int nImg, int nIn, bool shuffle, uint64_t seed, uint32_
     auto k = nIn <= 512 ? &k_pf_shuffle_perm<8> : nIn <= 1024 ? &k_pf_shuffle_perm<16>
                                                                : &k_pf_shuffle_perm<32>;
     hipLaunchKernelGGL(k, dim3(thx::cdiv(nImg, 4)), dim3(256), 0, s, nImg, nIn, seed, stream, perm, done);
+}
+
+// What one resampling step is given (k_pf_resample's arguments that differ
+// between its callers).
+struct Resample {
+    int nIn, nOut;                  // support sizes
+    const double* w; int ldw;       // the support's prior and its stride (0: one for all images)
+    const float* u; int ldu;        // the weights and their stride
+    uint32_t stream;                // Philox stream id of the shuffle and the draw
+    int* anc; double* wOut; int* top;   // ancestors, resampled priors, top particle
+    const int* cls = nullptr; int ldc = 0;   // class selection: u's row of image l is cls[l] * ldc on
+    const int* done = nullptr;      // images to skip
+    int* permOut = nullptr; double* u0Out = nullptr;   // thx_pf_resample's parity outputs
+};
+
+// One resampling step of every image: the shuffle's permutation where the
+// support needs it made ahead (shuffle_perm_launch), then k_pf_resample.
+// cdf / perm: nImg x nIn scratch each.
+int resample_launch(int nImg, bool shuffle, uint64_t seed, double* cdf, int* perm, hipStream_t s,
+                    const Resample& r)
+{
+    shuffle_perm_launch(nImg, r.nIn, shuffle, seed, r.stream, perm, r.done, s);
+    THX_LAUNCH_CHECK();
+    THX_LAUNCH(resample_kernel(r.nIn, shuffle), dim3(thx::cdiv(nImg, 4)), dim3(256),
+               resample_lds(r.nIn, shuffle), s, nImg, r.nIn, r.nOut, r.w, r.ldw, r.u, r.ldu,
+               seed, r.stream, r.anc, r.wOut, r.top, cdf, shuffle ? perm : nullptr,
+               r.permOut, r.u0Out, r.cls, r.ldc, r.done);
+    return THX_OK;
 }
 
 // gather ancestors: dst[l][j][:] = src[l (or shared)][anc[l][j]][:]
@@ -1773,10 +1764,7 @@ Plan plan(void* base, const thx_expect_cfg& c, int nImg, int nPxl, int nVisit, i
     thx::Carver k(base, ~size_t(0));
     Plan p;
     const int nK = c.nK > 0 ? c.nK : 1;
-    int nMax = c.nR > c.nT ? c.nR : c.nT;           // every resampled support size
-    if (c.mLR > nMax) nMax = c.mLR;
-    if (c.mLT > nMax) nMax = c.mLT;
-    if (mLD > nMax) nMax = mLD;
+    const int nMax = std::max({c.nR, c.nT, c.mLR, c.mLT, mLD});   // every resampled support size
     const bool scan = c.searchType == 0;
     p.rotP = k.take<float>(scan ? (size_t)2 * c.nR * nPxl : 0);
     p.gMat = k.take<double>(scan && !twoD ? (size_t)9 * c.nR : 0);
@@ -1787,8 +1775,7 @@ Plan plan(void* base, const thx_expect_cfg& c, int nImg, int nPxl, int nVisit, i
     p.gBase = k.take<float>(nImg);
     p.scanWsBytes = scan ? thx_global_scan_workspace(nImg, c.nR, c.nT, nPxl, c.algo) : 0;
     p.scanWs = k.take<char>(p.scanWsBytes);
-    p.anc = k.take<int>((size_t)nImg * (c.mLR > c.mLT ? (c.mLR > mLD ? c.mLR : mLD)
-                                                      : (c.mLT > mLD ? c.mLT : mLD)));
+    p.anc = k.take<int>((size_t)nImg * std::max({c.mLR, c.mLT, mLD}));
     p.ancR = k.take<int>((size_t)nImg * c.mLR);
     p.cdf = k.take<double>((size_t)nImg * nMax);
     p.perm = k.take<int>((size_t)nImg * nMax);
@@ -1920,9 +1907,8 @@ extern "C" int thx_pf_acg_mean(int nImg, int mR, const double* quat, int acgIter
     THX_CHECK_ARG(nImg >= 0 && mR > 0 && acgIters > 0, "thx_pf_acg_mean: bad sizes");
     THX_CHECK_ARG(nImg == 0 || (quat && meanQ), "thx_pf_acg_mean: null argument");
     if (nImg == 0) return THX_OK;
-    hipLaunchKernelGGL(k_pf_mean, dim3(thx::cdiv(nImg * GROUP, 256)), dim3(256), 0,
-                       thx::as_stream(stream), nImg, mR, quat, acgIters, nullptr, meanQ, iters);
-    THX_LAUNCH_CHECK();
+    THX_LAUNCH(k_pf_mean, dim3(thx::cdiv(nImg * GROUP, 256)), dim3(256), 0,
+               thx::as_stream(stream), nImg, mR, quat, acgIters, nullptr, meanQ, iters);
     return THX_OK;
 }
 
@@ -1932,9 +1918,8 @@ extern "C" int thx_pf_balance_rot(int nImg, int mR, const double* quat, double* 
     THX_CHECK_ARG(nImg >= 0 && mR > 0, "thx_pf_balance_rot: bad sizes");
     THX_CHECK_ARG(nImg == 0 || (quat && pR), "thx_pf_balance_rot: null argument");
     if (nImg == 0) return THX_OK;
-    hipLaunchKernelGGL(k_pf_balance_rot, dim3(thx::cdiv(nImg * GROUP, 256)), dim3(256), 0,
-                       thx::as_stream(stream), nImg, mR, quat, pR);
-    THX_LAUNCH_CHECK();
+    THX_LAUNCH(k_pf_balance_rot, dim3(thx::cdiv(nImg * GROUP, 256)), dim3(256), 0,
+               thx::as_stream(stream), nImg, mR, quat, pR);
     return THX_OK;
 }
 
@@ -1961,10 +1946,9 @@ extern "C" int thx_global_sample_set(int nR, int nT, double transS, unsigned lon
 {
     THX_CHECK_ARG(nR > 0 && nT > 1 && transS > 0.0 && quat && trans && pR && pT,
                   "thx_global_sample_set: bad arguments");
-    hipLaunchKernelGGL(k_sample_set, dim3(thx::cdiv(nR, 256)), dim3(256), 0,
-                       thx::as_stream(stream), nR, nT, transS, (uint64_t)seed, quat, trans, pR,
-                       pT, 0);
-    THX_LAUNCH_CHECK();
+    THX_LAUNCH(k_sample_set, dim3(thx::cdiv(nR, 256)), dim3(256), 0,
+               thx::as_stream(stream), nR, nT, transS, (uint64_t)seed, quat, trans, pR,
+               pT, 0);
     return THX_OK;
 }
 
@@ -1974,10 +1958,9 @@ extern "C" int thx_global_sample_set2d(int nR, int nT, double transS, unsigned l
 {
     THX_CHECK_ARG(nR > 0 && nT > 1 && transS > 0.0 && rot && trans && pR && pT,
                   "thx_global_sample_set2d: bad arguments");
-    hipLaunchKernelGGL(k_sample_set, dim3(thx::cdiv(nR, 256)), dim3(256), 0,
-                       thx::as_stream(stream), nR, nT, transS, (uint64_t)seed, rot, trans, pR,
-                       pT, 1);
-    THX_LAUNCH_CHECK();
+    THX_LAUNCH(k_sample_set, dim3(thx::cdiv(nR, 256)), dim3(256), 0,
+               thx::as_stream(stream), nR, nT, transS, (uint64_t)seed, rot, trans, pR,
+               pT, 1);
     return THX_OK;
 }
 
@@ -1988,9 +1971,8 @@ extern "C" int thx_pf_calvari2d(int nImg, int mR, const double* rot, int mT, con
     THX_CHECK_ARG(nImg >= 0 && mR > 0 && mT > 0, "thx_pf_calvari2d: bad sizes");
     THX_CHECK_ARG(nImg == 0 || (rot && trans && k && sd), "thx_pf_calvari2d: null argument");
     if (nImg == 0) return THX_OK;
-    hipLaunchKernelGGL(k_pf_calvari2d, dim3(thx::cdiv(nImg * GROUP, 256)), dim3(256), 0,
-                       thx::as_stream(stream), nImg, mR, rot, mT, trans, kFloor, sFloor, k, sd);
-    THX_LAUNCH_CHECK();
+    THX_LAUNCH(k_pf_calvari2d, dim3(thx::cdiv(nImg * GROUP, 256)), dim3(256), 0,
+               thx::as_stream(stream), nImg, mR, rot, mT, trans, kFloor, sFloor, k, sd);
     return THX_OK;
 }
 
@@ -2000,9 +1982,8 @@ extern "C" int thx_pf_balance_rot2d(int nImg, int mR, const double* rot, double*
     THX_CHECK_ARG(nImg >= 0 && mR > 0, "thx_pf_balance_rot2d: bad sizes");
     THX_CHECK_ARG(nImg == 0 || (rot && pR), "thx_pf_balance_rot2d: null argument");
     if (nImg == 0) return THX_OK;
-    hipLaunchKernelGGL(k_pf_balance_rot2d, dim3(thx::cdiv(nImg * GROUP, 256)), dim3(256), 0,
-                       thx::as_stream(stream), nImg, mR, rot, pR);
-    THX_LAUNCH_CHECK();
+    THX_LAUNCH(k_pf_balance_rot2d, dim3(thx::cdiv(nImg * GROUP, 256)), dim3(256), 0,
+               thx::as_stream(stream), nImg, mR, rot, pR);
     return THX_OK;
 }
 
@@ -2015,10 +1996,9 @@ extern "C" int thx_pf_perturb2d(int nImg, int mR, int mT, double* rot, double* t
     THX_CHECK_ARG(nImg == 0 || (rot && trans && pR && pT && k && sd),
                   "thx_pf_perturb2d: null argument");
     if (nImg == 0) return THX_OK;
-    hipLaunchKernelGGL(k_pf_perturb2d, dim3(thx::cdiv(nImg * GROUP, 256)), dim3(256), 0,
-                       thx::as_stream(stream), nImg, mR, mT, rot, trans, pR, pT, k, sd, pf, transS,
-                       transM, (uint64_t)seed, (uint32_t)stream_id, nullptr);
-    THX_LAUNCH_CHECK();
+    THX_LAUNCH(k_pf_perturb2d, dim3(thx::cdiv(nImg * GROUP, 256)), dim3(256), 0,
+               thx::as_stream(stream), nImg, mR, mT, rot, trans, pR, pT, k, sd, pf, transS,
+               transM, (uint64_t)seed, (uint32_t)stream_id, nullptr);
     return THX_OK;
 }
 
@@ -2030,10 +2010,9 @@ extern "C" int thx_pf_defocus(int nImg, int mD, int op, double arg, unsigned lon
     THX_CHECK_ARG(nImg == 0 || (d && (op == 2 || pD) && (op == 0 || sd)),
                   "thx_pf_defocus: null argument");
     if (nImg == 0) return THX_OK;
-    hipLaunchKernelGGL(k_pf_defocus, dim3(thx::cdiv(nImg * GROUP, 256)), dim3(256), 0,
-                       thx::as_stream(stream), nImg, mD, op, arg, (uint64_t)seed,
-                       (uint32_t)stream_id, d, pD, sd, nullptr);
-    THX_LAUNCH_CHECK();
+    THX_LAUNCH(k_pf_defocus, dim3(thx::cdiv(nImg * GROUP, 256)), dim3(256), 0,
+               thx::as_stream(stream), nImg, mD, op, arg, (uint64_t)seed,
+               (uint32_t)stream_id, d, pD, sd, nullptr);
     return THX_OK;
 }
 
@@ -2043,9 +2022,8 @@ extern "C" int thx_pf_peak(int nImg, int n, float* u, int ldu, double* peak, int
     THX_CHECK_ARG(nImg >= 0 && n > 0 && ldu >= n, "thx_pf_peak: bad sizes");
     THX_CHECK_ARG(nImg == 0 || (u && peak), "thx_pf_peak: null argument");
     if (nImg == 0) return THX_OK;
-    hipLaunchKernelGGL(k_pf_peak, dim3(thx::cdiv(nImg, 4)), dim3(256), 0,
-                       thx::as_stream(stream), nImg, n, u, ldu, peak, setFactor);
-    THX_LAUNCH_CHECK();
+    THX_LAUNCH(k_pf_peak, dim3(thx::cdiv(nImg, 4)), dim3(256), 0,
+               thx::as_stream(stream), nImg, n, u, ldu, peak, setFactor);
     return THX_OK;
 }
 
@@ -2072,32 +2050,66 @@ extern "C" int thx_pf_resample(int nImg, int nIn, int nOut, const double* w, int
     thx::Carver k(workspace, wsBytes);
     double* cdf = k.take<double>((size_t)nImg * nIn);
     int* pw = k.take<int>((size_t)nImg * nIn);
-    shuffle_perm_launch(nImg, nIn, shuffle, (uint64_t)seed, (uint32_t)stream_id, pw, nullptr,
-                        thx::as_stream(stream));
-    THX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(resample_kernel(nIn, shuffle), dim3(thx::cdiv(nImg, 4)), dim3(256), resample_lds(nIn, shuffle),
-                       thx::as_stream(stream),
-                       nImg, nIn, nOut, w, ldw, u, ldu, (uint64_t)seed, (uint32_t)stream_id, anc,
-                       wOut, iMax, cdf, shuffle ? pw : nullptr, perm, u0, nullptr, 0, nullptr);
-    THX_LAUNCH_CHECK();
-    return THX_OK;
+    return resample_launch(nImg, shuffle, (uint64_t)seed, cdf, pw, thx::as_stream(stream),
+                           {nIn, nOut, w, ldw, u, ldu, (uint32_t)stream_id, anc, wOut, iMax, nullptr,
+                            0, nullptr, perm, u0});
 }
 
 // calVari of a phase reads the pre-resample cloud and is only needed by the
-// next perturbation and the stopping rule, so it runs on a side stream
-// beside the resampling, the gathers and the next phase's inferACG mean --
-// two latency-bound, low-occupancy kernels side by side.  One side stream
-// and a fork / join event pair per (device, caller stream), made once; the
-// side stream only ever waits on events recorded on the caller's stream (a
-// fork / join pattern, the shape HIP graph capture accepts).
+// next perturbation and the stopping rule, so it runs on a side lane beside
+// the resampling, the gathers and the next phase's inferACG mean -- two
+// latency-bound, low-occupancy kernels side by side.  The mean has a lane of
+// its own.  Both lanes are made once per (device, caller stream); a lane only
+// ever waits on events recorded on the caller's stream (a fork / join
+// pattern, the shape HIP graph capture accepts).
 namespace {
-struct SideStream {
+// One side stream with its fork / join event pair.  open: forked and not yet
+// joined into the caller's stream.
+struct Lane {
     hipStream_t s = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
-    // the second side stream: the next phase's inferACG mean, forked once the
-    // rotations are resampled, beside the translations' resampling
-    hipStream_t s2 = nullptr;
-    hipEvent_t fork2 = nullptr, join2 = nullptr;
+    hipEvent_t forkEv = nullptr, joinEv = nullptr;
+    bool open = false;
+
+    // what the lane is given next runs after everything on main so far
+    int fork(hipStream_t main)
+    {
+        open = true;
+        THX_HIP(hipEventRecord(forkEv, main));
+        THX_HIP(hipStreamWaitEvent(s, forkEv, 0));
+        return THX_OK;
+    }
+    // right after the lane's last launch: what a later join waits for (an
+    // error return between fork and this leaves the lane to drain)
+    int recorded()
+    {
+        THX_HIP(hipEventRecord(joinEv, s));
+        return THX_OK;
+    }
+    // main waits for the lane's recorded work, if any is outstanding
+    int join(hipStream_t main)
+    {
+        if (open) THX_HIP(hipStreamWaitEvent(main, joinEv, 0));
+        open = false;
+        return THX_OK;
+    }
+    // at the driver's exit, error paths included: a lane still open leaves no
+    // work behind main -- the caller may free or reuse the workspace right after
+    void drain(hipStream_t main)
+    {
+        if (open) {
+            (void)hipEventRecord(joinEv, s);
+            (void)hipStreamWaitEvent(main, joinEv, 0);
+            (void)hipStreamSynchronize(s);
+        }
+        open = false;
+    }
+};
+
+struct SideStream {
+    Lane vari;          // calVari of the pre-resample cloud
+    // the next phase's inferACG mean, forked once the rotations are resampled,
+    // beside the translations' resampling
+    Lane mean;
     std::mutex mu;      // calls on one caller stream are ordered anyway
 };
 
@@ -2111,174 +2123,210 @@ int side_stream(hipStream_t main, SideStream** out)
     SideStream*& e = (*tab)[std::make_pair(dev, main)];
     if (!e) {
         SideStream* n = new SideStream;
-        THX_HIP(hipStreamCreateWithFlags(&n->s, hipStreamNonBlocking));
-        THX_HIP(hipEventCreateWithFlags(&n->fork, hipEventDisableTiming));
-        THX_HIP(hipEventCreateWithFlags(&n->join, hipEventDisableTiming));
-        THX_HIP(hipStreamCreateWithFlags(&n->s2, hipStreamNonBlocking));
-        THX_HIP(hipEventCreateWithFlags(&n->fork2, hipEventDisableTiming));
-        THX_HIP(hipEventCreateWithFlags(&n->join2, hipEventDisableTiming));
+        for (Lane* l : {&n->vari, &n->mean}) {
+            THX_HIP(hipStreamCreateWithFlags(&l->s, hipStreamNonBlocking));
+            THX_HIP(hipEventCreateWithFlags(&l->forkEv, hipEventDisableTiming));
+            THX_HIP(hipEventCreateWithFlags(&l->joinEv, hipEventDisableTiming));
+        }
         e = n;
     }
     *out = e;
     return THX_OK;
 }
-}  // namespace
 
-extern "C" size_t thx_expectation_workspace(const thx_expect_cfg* cfg, int nImg, int nPxl,
-                                            int nOrd)
-{
-    if (!cfg) return 0;
-    return plan(nullptr, *cfg, nImg, nPxl, nOrd > 0 ? nOrd : nPxl).bytes;
-}
+// The Philox stream ids of the driver's draws: the counter is (image, stream
+// id, a tag of the kind of draw, n).  The ids with "+ phase" take one value
+// per phase; maxPhase <= 1000 (checked) keeps their ranges apart.
+enum : uint32_t {
+    RNG_CLASS = 999u,           // reseed: the class draw (k_pf_class)
+    RNG_RESEED_R = 1000u,       // reseed: rotations' shuffle and resampling
+    RNG_RESEED_T = 1001u,       // reseed: translations' shuffle and resampling
+    RNG_SEED_ANCHOR = 1002u,    // symmetrise anchor of the calVari before the first phase
+    RNG_PERTURB = 2000u,        // + phase: perturbation of R and T
+    RNG_RESAMPLE_R = 3000u,     // + phase: rotations' shuffle and resampling
+    RNG_RESAMPLE_T = 4000u,     // + phase: translations' shuffle and resampling
+    // + phase: the symmetrise anchor of the phase's calVari and the defocus
+    // set's shuffle and resampling.  One id may serve both draws: their tags
+    // differ (0u in k_pf_symmetrise; 0x5f1e0000u | lane in k_pf_shuffle_perm,
+    // 0x5f1e and 0x5e5a in k_pf_resample), so the counters never meet
+    RNG_ANCHOR_AND_RESAMPLE_D = 5000u,
+    RNG_DEFOCUS = 6000u,        // + phase: initD / the defocus perturbation
+};
 
-extern "C" size_t thx_expectation_ctf_workspace(const thx_expect_cfg* cfg,
-                                                const thx_ctf_search_cfg* cs, int nImg,
-                                                int nPxl, int nOrd)
-{
-    if (!cfg || !cs || cs->mLD <= 0) return 0;
-    return plan(nullptr, *cfg, nImg, nPxl, nOrd > 0 ? nOrd : nPxl, cs->mLD).bytes;
-}
+// What the entry points hand the driver.  cs != NULL: SEARCH_TYPE_CTF
+// (searchType 2) -- a local search whose phases also sample nD = cs->mLD
+// defocus factors per image (src/Optimiser.cpp:1183-1616 with the
+// _searchType == SEARCH_TYPE_CTF branches).
+struct ExpectArgs {
+    const thx_expect_cfg* cfg;
+    const thx_ctf_search_cfg* cs;
+    const float* vol;
+    const double *gQuat, *gTrans, *gPR, *gPT;
+    const float *dat, *ctf, *sigRcp;
+    const int *iCol, *iRow, *pxOrder;
+    int nOrd, nPxl, nImg;
+    double *quat, *trans, *pR, *pT;
+    float* score;
+    int *cls, *nPhaseOut;
+    void* workspace;
+    size_t wsBytes;
+    thx_stream_t stream;
+    bool twoD;
 
-// cs != NULL: SEARCH_TYPE_CTF (searchType 2) -- a local search whose phases
-// also sample nD = cs->mLD defocus factors per image (src/Optimiser.cpp:
-// 1183-1616 with the _searchType == SEARCH_TYPE_CTF branches).
-static int expectation_impl(const thx_expect_cfg* cfg, const thx_ctf_search_cfg* cs,
-                            const float* vol, const double* gQuat, const double* gTrans,
-                            const double* gPR, const double* gPT, const float* dat,
-                            const float* ctf, const float* sigRcp, const int* iCol,
-                            const int* iRow, const int* pxOrder, int nOrd, int nPxl, int nImg,
-                            double* quat, double* trans, double* pR, double* pT, float* score,
-                            int* cls, int* nPhaseOut, void* workspace, size_t wsBytes,
-                            thx_stream_t stream, bool twoD = false)
-{
-    THX_CHECK_ARG(cfg && vol && dat && (ctf || cs) && sigRcp && iCol && iRow && quat && trans &&
-                      pR && pT,
-                  "thx_expectation: null argument");
-    const thx_expect_cfg& c = *cfg;
-    THX_CHECK_ARG(!twoD || !c.volCells, "thx_expectation2d: no cell projectee in MODE_2D");
-    const bool global = c.searchType == 0;
-    if (cs) {
-        THX_CHECK_ARG(c.searchType == 2, "thx_expectation_ctf: searchType must be 2 (SEARCH_TYPE_CTF)");
-        THX_CHECK_ARG(cs->mLD > 0 && cs->attr && cs->d && cs->pD && cs->ctfRefineS >= 0.0 &&
-                          (long)c.mLT * cs->mLD <= 1024,
-                      "thx_expectation_ctf: bad CTF-search configuration");
-    } else {
-        THX_CHECK_ARG(c.searchType == 0 || c.searchType == 1,
-                      "thx_expectation: searchType must be 0 or 1");
+    // argument validation (an empty batch, nImg == 0, is valid)
+    int check() const
+    {
+        THX_CHECK_ARG(cfg && vol && dat && (ctf || cs) && sigRcp && iCol && iRow && quat && trans &&
+                          pR && pT,
+                      "thx_expectation: null argument");
+        const thx_expect_cfg& c = *cfg;
+        THX_CHECK_ARG(!twoD || !c.volCells, "thx_expectation2d: no cell projectee in MODE_2D");
+        const bool global = c.searchType == 0;
+        if (cs) {
+            THX_CHECK_ARG(c.searchType == 2, "thx_expectation_ctf: searchType must be 2 (SEARCH_TYPE_CTF)");
+            THX_CHECK_ARG(cs->mLD > 0 && cs->attr && cs->d && cs->pD && cs->ctfRefineS >= 0.0 &&
+                              (long)c.mLT * cs->mLD <= 1024,
+                          "thx_expectation_ctf: bad CTF-search configuration");
+        } else {
+            THX_CHECK_ARG(c.searchType == 0 || c.searchType == 1,
+                          "thx_expectation: searchType must be 0 or 1");
+        }
+        THX_CHECK_ARG(!global || (gQuat && gTrans && gPR && gPT),
+                      "thx_expectation: a global search needs the global sample set");
+        THX_CHECK_ARG(c.mLR > 0 && c.mLT > 0 && c.vdim == c.pf * c.idim && nImg >= 0 && nImg <= 65535 &&
+                          nPxl > 0 && (!global || (c.nR > 0 && c.nT > 0)),
+                      "thx_expectation: bad configuration");
+        THX_CHECK_ARG(c.nK >= 1 && c.nK <= KMAX_CLASS, "thx_expectation: nK must be in [1, 64]");
+        THX_CHECK_ARG(!c.volCells || c.nK == 1, "thx_expectation: volCells needs nK == 1");
+        THX_CHECK_ARG(global || c.nK == 1 || cls,
+                      "thx_expectation: a K-class local search needs the particles' classes (cls)");
+        THX_CHECK_ARG(c.converge ? (c.minPhase >= 0 && c.maxPhase > c.minPhase && c.maxPhase <= 1000)
+                                 : (c.nPhase >= 0),
+                      "thx_expectation: bad phase counts");
+        THX_CHECK_ARG(c.perturbMean == 0 || c.perturbMean == 1, "thx_expectation: perturbMean must be 0 or 1");
+        THX_CHECK_ARG(c.perturbMean == 0 || c.acgIters > 0, "thx_expectation: acgIters must be > 0");
+        THX_CHECK_ARG(!global || c.nR <= 65535, "thx_expectation: nR > 65535");
+        // (an empty batch is valid whatever these two say: the driver returns at once)
+        THX_CHECK_ARG(nImg == 0 || !pxOrder || (nOrd > 0 && nOrd % 16 == 0),
+                      "thx_expectation: nOrd must be a positive multiple of 16");
+        THX_CHECK_ARG(nImg == 0 || (c.nSymElem >= 0 && c.nSymElem <= thx::SYM_MAX &&
+                                    (c.nSymElem == 0 || c.symQuat)),
+                      "thx_expectation: nSymElem 0 .. 64 with symQuat");
+        return THX_OK;
     }
-    const int mLD = cs ? cs->mLD : 0;
-    THX_CHECK_ARG(!global || (gQuat && gTrans && gPR && gPT),
-                  "thx_expectation: a global search needs the global sample set");
-    THX_CHECK_ARG(c.mLR > 0 && c.mLT > 0 && c.vdim == c.pf * c.idim && nImg >= 0 && nImg <= 65535 &&
-                      nPxl > 0 && (!global || (c.nR > 0 && c.nT > 0)),
-                  "thx_expectation: bad configuration");
-    THX_CHECK_ARG(c.nK >= 1 && c.nK <= KMAX_CLASS, "thx_expectation: nK must be in [1, 64]");
-    THX_CHECK_ARG(!c.volCells || c.nK == 1, "thx_expectation: volCells needs nK == 1");
-    THX_CHECK_ARG(global || c.nK == 1 || cls,
-                  "thx_expectation: a K-class local search needs the particles' classes (cls)");
-    THX_CHECK_ARG(c.converge ? (c.minPhase >= 0 && c.maxPhase > c.minPhase && c.maxPhase <= 1000)
-                             : (c.nPhase >= 0),
-                  "thx_expectation: bad phase counts");
-    THX_CHECK_ARG(c.perturbMean == 0 || c.perturbMean == 1, "thx_expectation: perturbMean must be 0 or 1");
-    THX_CHECK_ARG(c.perturbMean == 0 || c.acgIters > 0, "thx_expectation: acgIters must be > 0");
-    THX_CHECK_ARG(!global || c.nR <= 65535, "thx_expectation: nR > 65535");
-    if (nImg == 0) return THX_OK;
-    THX_CHECK_ARG(!pxOrder || (nOrd > 0 && nOrd % 16 == 0),
-                  "thx_expectation: nOrd must be a positive multiple of 16");
-    THX_CHECK_ARG(c.nSymElem >= 0 && c.nSymElem <= thx::SYM_MAX && (c.nSymElem == 0 || c.symQuat),
-                  "thx_expectation: nSymElem 0 .. 64 with symQuat");
-    const Plan p = plan(workspace, c, nImg, nPxl, pxOrder ? nOrd : nPxl, mLD, twoD);
-    THX_CHECK_ARG(workspace && p.bytes <= wsBytes, "thx_expectation: workspace too small");
-    hipStream_t s = thx::as_stream(stream);
-    SideStream* side = nullptr;
-    THX_RET(side_stream(s, &side));
-    std::lock_guard<std::mutex> sideLock(side->mu);
-    bool sidePending = false;      // a calVari on the side stream not yet joined
-    // every exit, error paths included, leaves no side-stream work behind the
-    // caller's stream: the caller may free or reuse the workspace right after
-    struct SideGuard {
-        SideStream* side;
-        hipStream_t s;
-        bool open = false;         // forked and not yet joined into s
-        bool open2 = false;        // the same for the second side stream
-        ~SideGuard()
-        {
-            if (open) {
-                (void)hipEventRecord(side->join, side->s);
-                (void)hipStreamWaitEvent(s, side->join, 0);
-                (void)hipStreamSynchronize(side->s);
-            }
-            if (open2) {
-                (void)hipEventRecord(side->join2, side->s2);
-                (void)hipStreamWaitEvent(s, side->join2, 0);
-                (void)hipStreamSynchronize(side->s2);
-            }
-        }
-    } sideGuard{side, s};
-    // the next phase's perturbation mean, already running on s2
-    bool meanAhead = false;
-    auto join2 = [&]() -> int {
-        if (sideGuard.open2) {
-            THX_HIP(hipEventRecord(side->join2, side->s2));
-            THX_HIP(hipStreamWaitEvent(s, side->join2, 0));
-            sideGuard.open2 = false;
-        }
-        return THX_OK;
-    };
-    auto fork = [&]() -> int {
-        sideGuard.open = true;
-        THX_HIP(hipEventRecord(side->fork, s));
-        THX_HIP(hipStreamWaitEvent(side->s, side->fork, 0));
-        return THX_OK;
-    };
-    auto join_rec = [&]() -> int {
-        THX_HIP(hipEventRecord(side->join, side->s));
-        sidePending = true;
-        return THX_OK;
-    };
-    auto join = [&]() -> int {
-        if (sidePending) THX_HIP(hipStreamWaitEvent(s, side->join, 0));
-        sidePending = false;
-        sideGuard.open = false;
-        return THX_OK;
-    };
-    const unsigned gImg = thx::cdiv(nImg, 4);
-    const unsigned gPf = thx::cdiv(nImg * GROUP, 256);
-    const unsigned gOne = thx::cdiv(nImg, 256);
-    const int nK = c.nK;
+};
+
+// One call of the driver: its arguments, what follows from them and what its
+// stages hand each other.  run() enqueues the stages in order.
+struct Expect : ExpectArgs {
+    const thx_expect_cfg& c;
+    const Plan& p;
+    Lane& vari;                 // calVari beside the resampling
+    Lane& mean;                 // the next phase's perturbation mean
+    const hipStream_t s = thx::as_stream(stream);
+    const bool global = c.searchType == 0;
+    const int mLD = cs ? cs->mLD : 0, nK = c.nK;
     const int nSym = twoD ? 0 : c.nSymElem;     // point-group symmetry: MODE_3D only
     // one class's projectee: a half-complex volume, or a half-complex image in 2D
     const size_t dimSize = (size_t)(c.vdim / 2 + 1) * c.vdim * (twoD ? 1 : c.vdim);
     const int rankDiv = twoD ? 2 : 8;      // setPeakFactor(PAR_R): PEAK_FACTOR_BASE (^3 in 3D)
-    int* clsD = cls ? cls : p.cls;
-    int* nPD = nPhaseOut ? nPhaseOut : p.nP;
-    const int* clsSel = nK > 1 ? clsD : nullptr;    // rows / volumes picked per image
+    const unsigned gImg = thx::cdiv(nImg, 4), gPf = thx::cdiv(nImg * GROUP, 256),
+                   gOne = thx::cdiv(nImg, 256);
+    int* const clsD = cls ? cls : p.cls;
+    int* const nPD = nPhaseOut ? nPhaseOut : p.nP;
+    const int* const clsSel = nK > 1 ? clsD : nullptr;    // rows / volumes picked per image
+    const int phase0 = global ? 1 : 0, nPh = c.converge ? c.maxPhase - phase0 : c.nPhase;
+    int ypairR = 0;             // radius of the compact y-pair ball (0: the whole copy)
+    const int* done = nullptr;  // the stopping rule's mask, from phase_setup on
+    thx_local_sel sel{nullptr, nullptr, clsSel, (long long)dimSize};
+    const int* ord = nullptr;   // the view order
+    // the route samples images in index order whatever the visiting order
+    // (the kernel a phase runs must not depend on it): every image without
+    // the stopping rule, the index-ordered active list with it
+    const int* sampleNone[2] = {nullptr, nullptr};
+    const int* sampleIdx[2] = {p.actIdx, p.nActIdx};
+    const int* const* routeSample = nullptr;
+    // the step plan of the box-less phase kernels: the tile order without its
+    // all-padding steps and the images' A_l, the same for every phase
+    const int* stepPlan[2] = {p.stepOrd, p.stepPlan};
+    bool planned = false;
+    // the particle clouds ping-pong between the caller's buffers and
+    // tmpQ / tmpT: a phase reads the current pair and the resampling gathers
+    // into the other (the pre-resample cloud stays readable for calVari and
+    // the mean without a copy); the caller's buffers get the last one
+    double *cq = quat, *ct = trans, *nq = p.tmpQ, *nt = p.tmpT;
+    bool meanAhead = false;     // the next phase's perturbation mean, already running on its lane
+
+    Expect(const ExpectArgs& a, const Plan& pl, SideStream& side)
+        : ExpectArgs(a), c(*a.cfg), p(pl), vari(side.vari), mean(side.mean)
+    {
+    }
+    // every exit, error paths included, leaves no work on a lane behind s
+    ~Expect()
+    {
+        vari.drain(s);
+        mean.drain(s);
+    }
+
+    int resample(const Resample& r)
+    {
+        return resample_launch(nImg, c.shuffle, c.seed, p.cdf, p.perm, s, r);
+    }
+
+    // calVari's symmetrise (src/Particle.cpp:1028-1036; a drawn particle as
+    // the anchor; MODE_3D only), then calVari of the cloud (q, t) on stream
+    // `on`, both for the images not in dn
+    int calvari(hipStream_t on, double* q, const double* t, uint32_t anchorRng, double kFloor,
+                double sFloor, const int* dn)
+    {
+        if (!twoD)
+            THX_RET(thx::pf_symmetrise_launch(nImg, c.mLR, q, 2, nullptr, c.symQuat, nSym, c.seed,
+                                              anchorRng, dn, s));
+        if (on != s) THX_RET(vari.fork(s));
+        THX_LAUNCH(twoD ? k_pf_calvari2d : k_pf_calvari, dim3(gPf), dim3(256), 0, on, nImg,
+                   c.mLR, q, c.mLT, t, kFloor, sFloor, p.kv, p.sv, dn, p.acgHist);
+        return on != s ? vari.recorded() : THX_OK;
+    }
+
+    // the active list in view order and, for the route's sample, in index order
+    int active_lists()
+    {
+        THX_LAUNCH(k_compact, dim3(1), dim3(1024), 0, s, nImg, p.done, p.act, p.nAct, ord);
+        if (ord && c.converge) {
+            THX_LAUNCH(k_compact, dim3(1), dim3(1024), 0, s, nImg, p.done, p.actIdx,
+                       p.nActIdx, nullptr);
+        }
+        return THX_OK;
+    }
+
     // the y-pair copy: the compact ball around the pixel ring (radius pf
     // r_max + 2 voxels, no wrap, a few MB instead of the whole 2x volume:
     // its pages stay in the TLBs and its lines in one region), or the whole
     // copy when the ball is the volume
-    int ypairR = 0;
-    if (p.ypair) {
+    int ypair_copies()
+    {
+        if (!p.ypair) return THX_OK;
         if (env_on("THX_YPAIR_BALL")) {
-            hipLaunchKernelGGL(k_max_r2, dim3(1), dim3(256), 0, s, iCol, iRow, nPxl, p.maxR2);
-            THX_LAUNCH_CHECK();
+            THX_LAUNCH(k_max_r2, dim3(1), dim3(256), 0, s, iCol, iRow, nPxl, p.maxR2);
             int r2 = 0;
             THX_HIP(hipMemcpyAsync(&r2, p.maxR2, sizeof(int), hipMemcpyDeviceToHost, s));
             THX_HIP(hipStreamSynchronize(s));
             const int R = (int)std::ceil(c.pf * std::sqrt((double)r2)) + 2;
-            if (R + 2 <= c.vdim / 2 + 1 && thx::ypair_ball_elems(R) <= dimSize) ypairR = R;
+            if (R + 2 <= c.vdim / 2 + 1 && thx_ypair_ball_elems(R) <= dimSize) ypairR = R;
         }
         for (int k = 0; k < nK; k++) {
             if (ypairR > 0)
-                THX_RET(thx::volume_ypair_ball(vol + 2 * dimSize * k, c.vdim, ypairR,
-                                               p.ypair + 4 * thx::ypair_ball_elems(ypairR) * k, s));
+                THX_RET(thx_volume_ypair_ball(vol + 2 * dimSize * k, c.vdim, ypairR,
+                                              p.ypair + 4 * thx_ypair_ball_elems(ypairR) * k, stream));
             else
                 THX_RET(thx_volume_ypair(vol + 2 * dimSize * k, c.vdim, p.ypair + 4 * dimSize * k,
                                          stream));
         }
+        return THX_OK;
     }
 
-    if (global) {
+    int global_reseed()
+    {
         // ---- global scan of every class (ExpectRotran + ExpectProject + ExpectGlobal3D
         // with kIdx = class, src/Optimiser.cpp:1815-1847)
         if (!twoD) THX_RET(thx_rotmat(gQuat, c.nR, p.gMat, stream));
@@ -2298,173 +2346,118 @@ static int expectation_impl(const thx_expect_cfg* cfg, const thx_ctf_search_cfg*
         // setPeakFactor + keepHalfHeightPeak (R), resample R and T of the drawn
         // class, calVari with the scan floors (OPTIMISER_SCAN_SET_MIN_STD_WITH_PERTURB)
         if (nK > 1) {
-            hipLaunchKernelGGL(k_pf_class, dim3(gOne), dim3(256), 0, s, nImg, nK, p.gWC, c.seed,
-                               999u, clsD);
-            THX_LAUNCH_CHECK();
+            THX_LAUNCH(k_pf_class, dim3(gOne), dim3(256), 0, s, nImg, nK, p.gWC, c.seed,
+                       RNG_CLASS, clsD);
         } else {
             THX_HIP(hipMemsetAsync(clsD, 0, sizeof(int) * nImg, s));
         }
-        hipLaunchKernelGGL(k_pf_peak, dim3(gImg), dim3(256), 0, s, nImg, c.nR, p.gWR, nK * c.nR,
-                           p.peakR, 1, clsSel, c.nR, nullptr, rankDiv);
-        THX_LAUNCH_CHECK();
-        shuffle_perm_launch(nImg, c.nR, c.shuffle, c.seed, 1000u, p.perm, nullptr, s);
-        THX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(resample_kernel(c.nR, c.shuffle), dim3(gImg), dim3(256), resample_lds(c.nR, c.shuffle), s,
-                           nImg, c.nR, c.mLR, gPR, 0,
-                           p.gWR, nK * c.nR, c.seed, 1000u, p.anc, pR, p.topR, p.cdf,
-                           c.shuffle ? p.perm : nullptr, nullptr, nullptr, clsSel, c.nR, nullptr);
-        THX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_gather, dim3(1024), dim3(256), 0, s, nImg, c.mLR, 4, gQuat, 0L, c.nR,
-                           p.anc, quat, nullptr);
-        THX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_top_copy, dim3(thx::cdiv(4 * nImg, 256)), dim3(256), 0, s, nImg, gQuat,
-                           0L, p.topR, p.topQ, nullptr);
-        THX_LAUNCH_CHECK();
-        shuffle_perm_launch(nImg, c.nT, c.shuffle, c.seed, 1001u, p.perm, nullptr, s);
-        THX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(resample_kernel(c.nT, c.shuffle), dim3(gImg), dim3(256), resample_lds(c.nT, c.shuffle), s,
-                           nImg, c.nT, c.mLT, gPT, 0,
-                           p.gWT, nK * c.nT, c.seed, 1001u, p.anc, pT, p.topT, p.cdf,
-                           c.shuffle ? p.perm : nullptr, nullptr, nullptr, clsSel, c.nT, nullptr);
-        THX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_gather, dim3(1024), dim3(256), 0, s, nImg, c.mLT, 2, gTrans, 0L, c.nT,
-                           p.anc, trans, nullptr);
-        THX_LAUNCH_CHECK();
+        THX_LAUNCH(k_pf_peak, dim3(gImg), dim3(256), 0, s, nImg, c.nR, p.gWR, nK * c.nR,
+                   p.peakR, 1, clsSel, c.nR, nullptr, rankDiv);
+        THX_RET(resample({c.nR, c.mLR, gPR, 0, p.gWR, nK * c.nR, RNG_RESEED_R, p.anc, pR, p.topR,
+                          clsSel, c.nR}));
+        THX_LAUNCH(k_gather, dim3(1024), dim3(256), 0, s, nImg, c.mLR, 4, gQuat, 0L, c.nR,
+                   p.anc, quat, nullptr);
+        THX_LAUNCH(k_top_copy, dim3(thx::cdiv(4 * nImg, 256)), dim3(256), 0, s, nImg, gQuat,
+                   0L, p.topR, p.topQ, nullptr);
+        THX_RET(resample({c.nT, c.mLT, gPT, 0, p.gWT, nK * c.nT, RNG_RESEED_T, p.anc, pT, p.topT,
+                          clsSel, c.nT}));
+        THX_LAUNCH(k_gather, dim3(1024), dim3(256), 0, s, nImg, c.mLT, 2, gTrans, 0L, c.nT,
+                   p.anc, trans, nullptr);
         // calVari with the scan floors, beside phase 1's inferACG mean (both only
-        // read the reseeded cloud); its symmetrise (src/Particle.cpp:1028-1036)
-        // first, on the stream both read from
-        if (!twoD)
-            THX_RET(thx::pf_symmetrise_launch(nImg, c.mLR, quat, 2, nullptr, c.symQuat, nSym, c.seed,
-                                              1002u, nullptr, s));
-        THX_RET(fork());
-        hipLaunchKernelGGL(twoD ? k_pf_calvari2d : k_pf_calvari, dim3(gPf), dim3(256), 0, side->s,
-                           nImg, c.mLR, quat, c.mLT, trans, c.kMin, c.sMin, p.kv, p.sv, nullptr,
-                           p.acgHist);
-        THX_LAUNCH_CHECK();
-        THX_RET(join_rec());
-    } else {
-        // ---- local search from the caller's particle state: its spreads
-        // (calVari on the given cloud) and, for the top-particle mean, calRank1st
+        // read the reseeded cloud); its symmetrise first, on the stream both read from
+        return calvari(vari.s, quat, trans, RNG_SEED_ANCHOR, c.kMin, c.sMin, nullptr);
+    }
+
+    // ---- local search from the caller's particle state: its spreads
+    // (calVari on the given cloud) and, for the top-particle mean, calRank1st
+    int local_seed()
+    {
         if (nK == 1 && !cls) THX_HIP(hipMemsetAsync(clsD, 0, sizeof(int) * nImg, s));
-        if (!twoD)
-            THX_RET(thx::pf_symmetrise_launch(nImg, c.mLR, quat, 2, nullptr, c.symQuat, nSym, c.seed,
-                                              1002u, nullptr, s));
-        hipLaunchKernelGGL(twoD ? k_pf_calvari2d : k_pf_calvari, dim3(gPf), dim3(256), 0, s, nImg,
-                           c.mLR, quat, c.mLT, trans, 0.0, 0.0, p.kv, p.sv, nullptr, p.acgHist);
-        THX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_top_by_weight, dim3(gOne), dim3(256), 0, s, nImg, c.mLR, quat, pR, p.topQ);
-        THX_LAUNCH_CHECK();
+        THX_RET(calvari(s, quat, trans, RNG_SEED_ANCHOR, 0.0, 0.0, nullptr));
+        THX_LAUNCH(k_top_by_weight, dim3(gOne), dim3(256), 0, s, nImg, c.mLR, quat, pR,
+                   p.topQ);
         // the rotation peak factor a fresh particle carries (resetPeakFactor,
         // src/Particle.cpp:1957-1962: PEAK_FACTOR_MIN); a global search sets it
         // in the reseed
-        hipLaunchKernelGGL(k_fill, dim3(64), dim3(256), 0, s, p.peakR, (long)nImg, 1e-3);
-        THX_LAUNCH_CHECK();
+        THX_LAUNCH(k_fill, dim3(64), dim3(256), 0, s, p.peakR, (long)nImg, 1e-3);
+        return THX_OK;
     }
-    if (cs) {
-        // allocPreCal's cSearch branch (src/Optimiser.cpp:8124-8170), once per call
-        THX_RET(thx_defocus_pre(cs->attr, nImg, iCol, iRow, nPxl, c.idim, p.freq, p.dfo, p.K1,
-                                p.K2, stream));
-    }
-    hipLaunchKernelGGL(k_fill, dim3(64), dim3(256), 0, s, p.pC, (long)nImg, 1.0);
-    THX_LAUNCH_CHECK();
 
-    // ---- particle-filter phases (src/Optimiser.cpp:1183-1616): perturb +
-    // balanceWeight, likelihood + marginals, keepHalfHeightPeak (R),
-    // calRank1st, calVari (pre-resample cloud), resample, stopping rule
-    const int phase0 = global ? 1 : 0;
-    const int nPh = c.converge ? c.maxPhase - phase0 : c.nPhase;
-    const int* done = nullptr;
-    // the phases' volume: the caller's cell copy or vol (with the y-pair copy
-    // for the device route)
-    const float* phaseVol = c.volCells ? c.volCells : vol;
-    const int phaseLayout = c.volCells ? 1 : 0;
-    thx_local_sel sel{nullptr, nullptr, clsSel, (long long)dimSize};
-    // 3D phases visit the images in view order (order.hip), through the
-    // active list; results per image are unchanged
-    const int* ord = nullptr;
-    if (!twoD && nPh > 0 && view_order_on()) {
-        THX_RET(thx::view_order(nImg, c.mLR, quat, p.ordKey, p.ordKeyOut, p.ordIdx, p.ord, p.ordTmp,
-                                p.ordTmpBytes, s));
-        ord = p.ord;
-    }
-    // the route samples images in index order whatever the visiting order
-    // (the kernel a phase runs must not depend on it): every image without
-    // the stopping rule, the index-ordered active list with it
-    const int* sampleNone[2] = {nullptr, nullptr};
-    const int* sampleIdx[2] = {p.actIdx, p.nActIdx};
-    const int* const* routeSample = ord ? (c.converge ? sampleIdx : sampleNone) : nullptr;
-    if (c.converge || ord) {
-        THX_HIP(hipMemsetAsync(p.done, 0, sizeof(int) * nImg, s));
-        hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, nImg, p.done, p.act, p.nAct, ord);
-        THX_LAUNCH_CHECK();
-        if (ord && c.converge) {
-            hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, nImg, p.done, p.actIdx, p.nActIdx,
-                               nullptr);
-            THX_LAUNCH_CHECK();
+    // what the phases share: the CTF search's tables, the view order, the
+    // active lists and the step plan
+    int phase_setup()
+    {
+        if (cs) {
+            // allocPreCal's cSearch branch (src/Optimiser.cpp:8124-8170), once per call
+            THX_RET(thx_defocus_pre(cs->attr, nImg, iCol, iRow, nPxl, c.idim, p.freq, p.dfo, p.K1,
+                                    p.K2, stream));
         }
-        if (c.converge) done = p.done;
-        sel.active = p.act;
-        sel.nActive = p.nAct;
+        THX_LAUNCH(k_fill, dim3(64), dim3(256), 0, s, p.pC, (long)nImg, 1.0);
+        // 3D phases visit the images in view order (order.hip), through the
+        // active list; results per image are unchanged
+        if (!twoD && nPh > 0 && env_on("THX_VIEW_ORDER")) {
+            THX_RET(thx::view_order(nImg, c.mLR, quat, p.ordKey, p.ordKeyOut, p.ordIdx, p.ord,
+                                    p.ordTmp, p.ordTmpBytes, s));
+            ord = p.ord;
+        }
+        routeSample = ord ? (c.converge ? sampleIdx : sampleNone) : nullptr;
+        if (c.converge || ord) {
+            THX_HIP(hipMemsetAsync(p.done, 0, sizeof(int) * nImg, s));
+            THX_RET(active_lists());
+            if (c.converge) done = p.done;
+            sel.active = p.act;
+            sel.nActive = p.nAct;
+        }
+        if (!twoD && nPh > 0) {
+            int st = THX_OK;
+            planned = thx::step_plan_build(pxOrder, nOrd, dat, sigRcp, nPxl, nImg, mLD, p.stepOrd,
+                                           p.stepPlan, s, &st);
+            THX_RET(st);
+        }
+        return THX_OK;
     }
-    // the step plan of the box-less phase kernels: the tile order without its
-    // all-padding steps and the images' A_l, the same for every phase
-    const int* stepPlan[2] = {p.stepOrd, p.stepPlan};
-    bool planned = false;
-    if (!twoD && nPh > 0) {
-        int st = THX_OK;
-        planned = thx::step_plan_build(pxOrder, nOrd, dat, sigRcp, nPxl, nImg, mLD, p.stepOrd,
-                                       p.stepPlan, s, &st);
-        THX_RET(st);
-    }
-    // the particle clouds ping-pong between the caller's buffers and
-    // tmpQ / tmpT: a phase reads the current pair and the resampling gathers
-    // into the other (the pre-resample cloud stays readable for calVari and
-    // the mean without a copy); the caller's buffers get the last one
-    double* cq = quat;
-    double* ct = trans;
-    double* nq = p.tmpQ;
-    double* nt = p.tmpT;
-    for (int phase = phase0; phase < phase0 + nPh; phase++) {
+
+    // perturb + balanceWeight (R, T), and the defocus set's with a CTF search
+    int perturb(int phase)
+    {
         const bool large = phase == phase0 && (!global || c.largeFirst);
-        if (twoD) {
-            // MODE_2D perturb (von Mises, no mean) + balanceWeight (R, T)
-            THX_RET(join());
-            hipLaunchKernelGGL(k_pf_perturb2d, dim3(gPf), dim3(256), 0, s, nImg, c.mLR, c.mLT, cq,
-                               ct, pR, pT, p.kv, p.sv,
-                               large ? c.perturbFactorL : c.perturbFactor, c.transS, c.transM,
-                               c.seed, (uint32_t)(2000 + phase), done);
-            THX_LAUNCH_CHECK();
-        } else if (c.perturbMean == 1) {
+        const double factor = large ? c.perturbFactorL : c.perturbFactor;
+        if (!twoD && c.perturbMean == 1) {
             if (meanAhead) {
-                THX_RET(join2());      // forked after the last phase's rotation resampling
+                THX_RET(mean.join(s));      // forked after the last phase's rotation resampling
                 meanAhead = false;
             } else {
-                hipLaunchKernelGGL(k_pf_mean, dim3(gPf), dim3(256), 0, s, nImg, c.mLR, cq,
-                                   c.acgIters, done, p.meanQ, nullptr);
-                THX_LAUNCH_CHECK();
+                THX_LAUNCH(k_pf_mean, dim3(gPf), dim3(256), 0, s, nImg, c.mLR, cq,
+                           c.acgIters, done, p.meanQ, nullptr);
             }
         }
-        if (!twoD) {
-            THX_RET(join());     // the spreads of the previous calVari
-            hipLaunchKernelGGL(k_pf_perturb, dim3(gPf), dim3(256), 0, s, nImg, c.mLR, c.mLT, cq,
-                               ct, pR, pT, p.topQ, p.kv, p.sv,
-                               large ? c.perturbFactorL : c.perturbFactor, c.transS, c.transM,
-                               c.seed, (uint32_t)(2000 + phase), c.perturbMean, p.meanQ, done,
-                               c.symQuat, nSym);
-            THX_LAUNCH_CHECK();
-        }
+        THX_RET(vari.join(s));     // the spreads of the previous calVari
+        if (twoD)   // MODE_2D perturb (von Mises, no mean) + balanceWeight (R, T)
+            THX_LAUNCH(k_pf_perturb2d, dim3(gPf), dim3(256), 0, s, nImg, c.mLR, c.mLT, cq,
+                       ct, pR, pT, p.kv, p.sv, factor, c.transS, c.transM, c.seed,
+                       (uint32_t)(RNG_PERTURB + phase), done);
+        else
+            THX_LAUNCH(k_pf_perturb, dim3(gPf), dim3(256), 0, s, nImg, c.mLR, c.mLT, cq,
+                       ct, pR, pT, p.topQ, p.kv, p.sv, factor, c.transS, c.transM, c.seed,
+                       (uint32_t)(RNG_PERTURB + phase), c.perturbMean, p.meanQ, done,
+                       c.symQuat, nSym);
         if (cs) {
             // phase 0: initD(mLD, ctfRefineS); later: perturb(perturbFactorSCTF,
             // PAR_D) (src/Optimiser.cpp:1194-1195, 1208-1209); then the phase's
             // CTF per defocus sample (:1248-1273)
-            hipLaunchKernelGGL(k_pf_defocus, dim3(gPf), dim3(256), 0, s, nImg, mLD,
-                               phase == phase0 ? 0 : 1,
-                               phase == phase0 ? cs->ctfRefineS : cs->perturbFactorSCTF, c.seed,
-                               (uint32_t)(6000 + phase), cs->d, cs->pD, p.sdD, done);
-            THX_LAUNCH_CHECK();
+            THX_LAUNCH(k_pf_defocus, dim3(gPf), dim3(256), 0, s, nImg, mLD,
+                       phase == phase0 ? 0 : 1,
+                       phase == phase0 ? cs->ctfRefineS : cs->perturbFactorSCTF, c.seed,
+                       (uint32_t)(RNG_DEFOCUS + phase), cs->d, cs->pD, p.sdD, done);
             THX_RET(thx_ctf_search(p.dfo, p.freq, cs->d, mLD, p.K1, p.K2, cs->attr, nImg, nPxl,
                                    p.ctfD, stream));
         }
+        return THX_OK;
+    }
+
+    // fused projection + likelihood + marginals of the current cloud
+    int likelihood(int phase)
+    {
         const int pi = phase - phase0;
         // phases past the caller's event pairs run untimed
         hipEvent_t* ev = pi < c.nPhaseEvents ? static_cast<hipEvent_t*>(c.phaseEvents) : nullptr;
@@ -2477,43 +2470,29 @@ static int expectation_impl(const thx_expect_cfg* cfg, const thx_ctf_search_cfg*
                                               mLD, cs ? cs->pD : nullptr, p.wD, sel.active,
                                               sel.nActive));
             if (ev) THX_HIP(hipEventRecord(ev[2 * pi + 1], s));
-        } else
-        THX_RET(thx::local_phase_timed(&sel, ev ? ev[2 * pi] : nullptr, ev ? ev[2 * pi + 1] : nullptr,
-                                       phaseVol, phaseLayout, c.vdim,
-                                       c.pf, cq, c.mLR, ct, c.mLT, p.pC, pR, pT,
-                                       dat, cs ? p.ctfD : ctf, sigRcp, iCol, iRow, pxOrder, nOrd,
-                                       nPxl, c.idim, nImg, p.wC, p.wR, p.wT, p.base, p.localWs,
-                                       p.localWsBytes, stream, mLD, cs ? cs->pD : nullptr, p.wD,
-                                       p.ypair, pi < c.nPhaseRoute ? c.phaseRoute + pi : nullptr,
-                                       routeSample, ypairR, planned ? stepPlan : nullptr));
-        hipLaunchKernelGGL(k_pf_peak, dim3(gImg), dim3(256), 0, s, nImg, c.mLR, p.wR, c.mLR,
-                           p.peakR, 0, nullptr, 0, done, rankDiv);
-        THX_LAUNCH_CHECK();
-        // calVari's symmetrise (a drawn particle as the anchor) on the cloud the
-        // resampling gathers from, then the pre-resample cloud, kept for calVari
-        // and the gathers
-        if (!twoD)
-            THX_RET(thx::pf_symmetrise_launch(nImg, c.mLR, cq, 2, nullptr, c.symQuat, nSym, c.seed,
-                                              (uint32_t)(5000 + phase), done, s));
-        // calVari of the pre-resample cloud on the side stream (needed by the next
-        // perturbation and the stopping rule only)
-        THX_RET(fork());
-        hipLaunchKernelGGL(twoD ? k_pf_calvari2d : k_pf_calvari, dim3(gPf), dim3(256), 0, side->s,
-                           nImg, c.mLR, cq, c.mLT, ct, 0.0, 0.0, p.kv, p.sv, done,
-                           p.acgHist);
-        THX_LAUNCH_CHECK();
-        THX_RET(join_rec());
-        // resample R and T by the phase marginals; ancestors gathered in place
-        shuffle_perm_launch(nImg, c.mLR, c.shuffle, c.seed, (uint32_t)(3000 + phase), p.perm, done, s);
-        THX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(resample_kernel(c.mLR, c.shuffle), dim3(gImg), dim3(256), resample_lds(c.mLR, c.shuffle), s,
-                           nImg, c.mLR, c.mLR, pR,
-                           c.mLR, p.wR, c.mLR, c.seed, (uint32_t)(3000 + phase), p.ancR, pR,
-                           p.topR, p.cdf, c.shuffle ? p.perm : nullptr, nullptr, nullptr, nullptr,
-                           0, done);
-        THX_LAUNCH_CHECK();
+            return THX_OK;
+        }
+        // the phases' volume: the caller's cell copy or vol (with the y-pair copy
+        // for the device route)
+        return thx::local_phase_impl(&sel, ev ? ev[2 * pi] : nullptr, ev ? ev[2 * pi + 1] : nullptr,
+                                     c.volCells ? c.volCells : vol, c.volCells ? 1 : 0, c.vdim,
+                                     c.pf, cq, c.mLR, ct, c.mLT, p.pC, pR, pT,
+                                     dat, cs ? p.ctfD : ctf, sigRcp, iCol, iRow, pxOrder, nOrd,
+                                     nPxl, c.idim, nImg, p.wC, p.wR, p.wT, p.base, nullptr,
+                                     p.localWs, p.localWsBytes, stream, mLD,
+                                     cs ? cs->pD : nullptr, p.wD, p.ypair,
+                                     pi < c.nPhaseRoute ? c.phaseRoute + pi : nullptr, routeSample,
+                                     ypairR, planned ? stepPlan : nullptr);
+    }
+
+    // resample R and T (and D) by the phase marginals; ancestors gathered into
+    // the other pair of the ping-pong
+    int resample_phase(int phase)
+    {
+        THX_RET(resample({c.mLR, c.mLR, pR, c.mLR, p.wR, c.mLR, RNG_RESAMPLE_R + phase, p.ancR, pR,
+                          p.topR, nullptr, 0, done}));
         // the next phase's perturbation mean needs only the resampled
-        // rotations: it runs on s2 beside the gathers and the translations'
+        // rotations: it runs on its lane beside the gathers and the translations'
         // resampling, reading the pre-resample cloud through the ancestors (an
         // image the stopping rule retires below gets a mean nothing reads).
         // It reads the done mask as of the fork (a snapshot), never the
@@ -2522,66 +2501,62 @@ static int expectation_impl(const thx_expect_cfg* cfg, const thx_ctf_search_cfg*
             if (done)
                 THX_HIP(hipMemcpyAsync(p.doneSnap, done, sizeof(int) * nImg,
                                        hipMemcpyDeviceToDevice, s));
-            THX_HIP(hipEventRecord(side->fork2, s));
-            THX_HIP(hipStreamWaitEvent(side->s2, side->fork2, 0));
-            sideGuard.open2 = true;
-            hipLaunchKernelGGL(k_pf_mean, dim3(gPf), dim3(256), 0, side->s2, nImg, c.mLR, cq,
-                               c.acgIters, done ? p.doneSnap : nullptr, p.meanQ, nullptr, p.ancR);
-            THX_LAUNCH_CHECK();
+            THX_RET(mean.fork(s));
+            THX_LAUNCH(k_pf_mean, dim3(gPf), dim3(256), 0, mean.s, nImg, c.mLR, cq,
+                       c.acgIters, done ? p.doneSnap : nullptr, p.meanQ, nullptr, p.ancR);
+            THX_RET(mean.recorded());
             meanAhead = true;
         }
-        hipLaunchKernelGGL(k_gather, dim3(1024), dim3(256), 0, s, nImg, c.mLR, 4, (const double*)cq,
-                           (long)c.mLR * 4, c.mLR, p.ancR, nq, done, 1);
-        THX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_top_copy, dim3(thx::cdiv(4 * nImg, 256)), dim3(256), 0, s, nImg,
-                           cq, (long)c.mLR * 4, p.topR, p.topQ, done);
-        THX_LAUNCH_CHECK();
-        shuffle_perm_launch(nImg, c.mLT, c.shuffle, c.seed, (uint32_t)(4000 + phase), p.perm, done, s);
-        THX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(resample_kernel(c.mLT, c.shuffle), dim3(gImg), dim3(256), resample_lds(c.mLT, c.shuffle), s,
-                           nImg, c.mLT, c.mLT, pT,
-                           c.mLT, p.wT, c.mLT, c.seed, (uint32_t)(4000 + phase), p.anc, pT,
-                           p.topT, p.cdf, c.shuffle ? p.perm : nullptr, nullptr, nullptr, nullptr,
-                           0, done);
-        THX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_gather, dim3(1024), dim3(256), 0, s, nImg, c.mLT, 2, (const double*)ct,
-                           (long)c.mLT * 2, c.mLT, p.anc, nt, done, 1);
-        THX_LAUNCH_CHECK();
+        THX_LAUNCH(k_gather, dim3(1024), dim3(256), 0, s, nImg, c.mLR, 4, (const double*)cq,
+                   (long)c.mLR * 4, c.mLR, p.ancR, nq, done, 1);
+        THX_LAUNCH(k_top_copy, dim3(thx::cdiv(4 * nImg, 256)), dim3(256), 0, s, nImg,
+                   cq, (long)c.mLR * 4, p.topR, p.topQ, done);
+        THX_RET(resample({c.mLT, c.mLT, pT, c.mLT, p.wT, c.mLT, RNG_RESAMPLE_T + phase, p.anc, pT,
+                          p.topT, nullptr, 0, done}));
+        THX_LAUNCH(k_gather, dim3(1024), dim3(256), 0, s, nImg, c.mLT, 2, (const double*)ct,
+                   (long)c.mLT * 2, c.mLT, p.anc, nt, done, 1);
         // the resampled clouds are current from here
         std::swap(cq, nq);
         std::swap(ct, nt);
         if (cs) {
             // calRank1st, calVari, resample (mLD, PAR_D) (src/Optimiser.cpp:1483-1488);
             // no peak factor (OPTIMISER_PEAK_FACTOR_D is off, include/Config.h:220)
-            hipLaunchKernelGGL(k_pf_defocus, dim3(gPf), dim3(256), 0, s, nImg, mLD, 2, 0.0, c.seed,
-                               0u, cs->d, cs->pD, p.sdD, done);
-            THX_LAUNCH_CHECK();
-            shuffle_perm_launch(nImg, mLD, c.shuffle, c.seed, (uint32_t)(5000 + phase), p.perm, done, s);
-            THX_LAUNCH_CHECK();
-            hipLaunchKernelGGL(resample_kernel(mLD, c.shuffle), dim3(gImg), dim3(256), resample_lds(mLD, c.shuffle),
-                               s, nImg, mLD, mLD, cs->pD, mLD, p.wD, mLD, c.seed,
-                               (uint32_t)(5000 + phase), p.anc, cs->pD, p.topD, p.cdf,
-                               c.shuffle ? p.perm : nullptr, nullptr, nullptr, nullptr, 0, done);
-            THX_LAUNCH_CHECK();
+            THX_LAUNCH(k_pf_defocus, dim3(gPf), dim3(256), 0, s, nImg, mLD, 2, 0.0, c.seed,
+                       0u, cs->d, cs->pD, p.sdD, done);
+            THX_RET(resample({mLD, mLD, cs->pD, mLD, p.wD, mLD, RNG_ANCHOR_AND_RESAMPLE_D + phase,
+                              p.anc, cs->pD, p.topD, nullptr, 0, done}));
             THX_HIP(hipMemcpyAsync(p.tmpD, cs->d, sizeof(double) * nImg * mLD,
                                    hipMemcpyDeviceToDevice, s));
-            hipLaunchKernelGGL(k_gather, dim3(1024), dim3(256), 0, s, nImg, mLD, 1, p.tmpD,
-                               (long)mLD, mLD, p.anc, cs->d, done);
-            THX_LAUNCH_CHECK();
+            THX_LAUNCH(k_gather, dim3(1024), dim3(256), 0, s, nImg, mLD, 1, p.tmpD,
+                       (long)mLD, mLD, p.anc, cs->d, done);
         }
-        if (c.converge) {
-            THX_RET(join());
-            hipLaunchKernelGGL(k_pf_converge, dim3(gOne), dim3(256), 0, s, nImg, phase, c.minPhase,
-                               phase0 + nPh - 1, p.kv, p.sv, p.bestR, p.bestT, p.done, nPD,
-                               cs ? p.sdD : nullptr, cs ? p.bestD : nullptr, (int)twoD);
-            THX_LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, nImg, p.done, p.act, p.nAct, ord);
-            THX_LAUNCH_CHECK();
-            if (ord) {
-                hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, nImg, p.done, p.actIdx,
-                                   p.nActIdx, nullptr);
-                THX_LAUNCH_CHECK();
-            }
+        return THX_OK;
+    }
+
+    int run()
+    {
+        THX_RET(ypair_copies());
+        THX_RET(global ? global_reseed() : local_seed());
+        THX_RET(phase_setup());
+        // ---- particle-filter phases (src/Optimiser.cpp:1183-1616): perturb +
+        // balanceWeight, likelihood + marginals, keepHalfHeightPeak (R),
+        // calRank1st, calVari (pre-resample cloud), resample, stopping rule
+        for (int phase = phase0; phase < phase0 + nPh; phase++) {
+            THX_RET(perturb(phase));
+            THX_RET(likelihood(phase));
+            THX_LAUNCH(k_pf_peak, dim3(gImg), dim3(256), 0, s, nImg, c.mLR, p.wR, c.mLR,
+                       p.peakR, 0, nullptr, 0, done, rankDiv);
+            // calVari of the pre-resample cloud on its lane (needed by the next
+            // perturbation and the stopping rule only), its symmetrise on the
+            // cloud the resampling gathers from
+            THX_RET(calvari(vari.s, cq, ct, RNG_ANCHOR_AND_RESAMPLE_D + phase, 0.0, 0.0, done));
+            THX_RET(resample_phase(phase));
+            if (!c.converge) continue;
+            THX_RET(vari.join(s));
+            THX_LAUNCH(k_pf_converge, dim3(gOne), dim3(256), 0, s, nImg, phase, c.minPhase,
+                       phase0 + nPh - 1, p.kv, p.sv, p.bestR, p.bestT, p.done, nPD,
+                       cs ? p.sdD : nullptr, cs ? p.bestD : nullptr, (int)twoD);
+            THX_RET(active_lists());
             if (phase >= c.minPhase) {
                 int left = 0;
                 THX_HIP(hipMemcpyAsync(&left, p.nAct, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -2589,24 +2564,56 @@ static int expectation_impl(const thx_expect_cfg* cfg, const thx_ctf_search_cfg*
                 if (left == 0) break;
             }
         }
+        THX_RET(vari.join(s));     // nothing of this call stays on the side lanes
+        THX_RET(mean.join(s));
+        if (cq != quat) {
+            THX_HIP(hipMemcpyAsync(quat, cq, sizeof(double) * nImg * c.mLR * 4,
+                                   hipMemcpyDeviceToDevice, s));
+            THX_HIP(hipMemcpyAsync(trans, ct, sizeof(double) * nImg * c.mLT * 2,
+                                   hipMemcpyDeviceToDevice, s));
+        }
+        if (!c.converge) {
+            THX_LAUNCH(k_fill_int, dim3(64), dim3(256), 0, s, nPD, (long)nImg,
+                       phase0 + c.nPhase - 1);
+        }
+        if (score) {
+            // per-image score: the last phase's baseline (the scan's without phases)
+            THX_HIP(hipMemcpyAsync(score, nPh > 0 ? p.base : p.gBase, sizeof(float) * nImg,
+                                   hipMemcpyDeviceToDevice, s));
+        }
+        return THX_OK;
     }
-    THX_RET(join());     // nothing of this call stays on the side streams
-    THX_RET(join2());
-    if (cq != quat) {
-        THX_HIP(hipMemcpyAsync(quat, cq, sizeof(double) * nImg * c.mLR * 4, hipMemcpyDeviceToDevice, s));
-        THX_HIP(hipMemcpyAsync(trans, ct, sizeof(double) * nImg * c.mLT * 2, hipMemcpyDeviceToDevice, s));
-    }
-    if (!c.converge) {
-        hipLaunchKernelGGL(k_fill_int, dim3(64), dim3(256), 0, s, nPD, (long)nImg,
-                           phase0 + c.nPhase - 1);
-        THX_LAUNCH_CHECK();
-    }
-    if (score) {
-        // per-image score: the last phase's baseline (the scan's without phases)
-        THX_HIP(hipMemcpyAsync(score, nPh > 0 ? p.base : p.gBase, sizeof(float) * nImg,
-                               hipMemcpyDeviceToDevice, s));
-    }
-    return THX_OK;
+};
+
+int expectation_impl(const ExpectArgs& a)
+{
+    THX_RET(a.check());
+    if (a.nImg == 0) return THX_OK;
+    const Plan p = plan(a.workspace, *a.cfg, a.nImg, a.nPxl, a.pxOrder ? a.nOrd : a.nPxl,
+                        a.cs ? a.cs->mLD : 0, a.twoD);
+    THX_CHECK_ARG(a.workspace && p.bytes <= a.wsBytes, "thx_expectation: workspace too small");
+    SideStream* side = nullptr;
+    THX_RET(side_stream(thx::as_stream(a.stream), &side));
+    std::lock_guard<std::mutex> sideLock(side->mu);
+    return Expect(a, p, *side).run();
+}
+
+
+}  // namespace
+
+extern "C" size_t thx_expectation_workspace(const thx_expect_cfg* cfg, int nImg, int nPxl,
+                                            int nOrd)
+{
+    if (!cfg) return 0;
+    return plan(nullptr, *cfg, nImg, nPxl, nOrd > 0 ? nOrd : nPxl).bytes;
+}
+
+extern "C" size_t thx_expectation_ctf_workspace(const thx_expect_cfg* cfg,
+                                                const thx_ctf_search_cfg* cs, int nImg,
+                                                int nPxl, int nOrd)
+{
+    if (!cfg || !cs || cs->mLD <= 0) return 0;
+    return plan(nullptr, *cfg, nImg, nPxl, nOrd > 0 ? nOrd : nPxl, cs->mLD).bytes;
 }
 
 extern "C" int thx_expectation(const thx_expect_cfg* cfg, const float* vol,
@@ -2620,9 +2627,9 @@ extern "C" int thx_expectation(const thx_expect_cfg* cfg, const float* vol,
                                float* score, int* cls, int* nPhaseOut, void* workspace,
                                size_t wsBytes, thx_stream_t stream)
 {
-    return expectation_impl(cfg, nullptr, vol, gQuat, gTrans, gPR, gPT, dat, ctf, sigRcp, iCol,
-                            iRow, pxOrder, nOrd, nPxl, nImg, quat, trans, pR, pT, score, cls,
-                            nPhaseOut, workspace, wsBytes, stream);
+    return expectation_impl({cfg, nullptr, vol, gQuat, gTrans, gPR, gPT, dat, ctf, sigRcp, iCol,
+                             iRow, pxOrder, nOrd, nPxl, nImg, quat, trans, pR, pT, score, cls,
+                             nPhaseOut, workspace, wsBytes, stream, false});
 }
 
 // MODE_2D (src/Optimiser.cpp's _para.mode == MODE_2D branches of
@@ -2642,9 +2649,9 @@ extern "C" int thx_expectation2d(const thx_expect_cfg* cfg, const float* vol, co
                                  int* nPhaseOut, void* workspace, size_t wsBytes,
                                  thx_stream_t stream)
 {
-    return expectation_impl(cfg, nullptr, vol, gRot, gTrans, gPR, gPT, dat, ctf, sigRcp, iCol,
-                            iRow, nullptr, 0, nPxl, nImg, rot, trans, pR, pT, score, cls,
-                            nPhaseOut, workspace, wsBytes, stream, true);
+    return expectation_impl({cfg, nullptr, vol, gRot, gTrans, gPR, gPT, dat, ctf, sigRcp, iCol,
+                             iRow, nullptr, 0, nPxl, nImg, rot, trans, pR, pT, score, cls,
+                             nPhaseOut, workspace, wsBytes, stream, true});
 }
 
 extern "C" size_t thx_expectation2d_ctf_workspace(const thx_expect_cfg* cfg,
@@ -2662,9 +2669,9 @@ extern "C" int thx_expectation2d_ctf(const thx_expect_cfg* cfg, const thx_ctf_se
                                      size_t wsBytes, thx_stream_t stream)
 {
     THX_CHECK_ARG(cs, "thx_expectation2d_ctf: null CTF-search configuration");
-    return expectation_impl(cfg, cs, vol, nullptr, nullptr, nullptr, nullptr, dat, nullptr,
-                            sigRcp, iCol, iRow, nullptr, 0, nPxl, nImg, rot, trans, pR, pT, score,
-                            cls, nPhaseOut, workspace, wsBytes, stream, true);
+    return expectation_impl({cfg, cs, vol, nullptr, nullptr, nullptr, nullptr, dat, nullptr,
+                             sigRcp, iCol, iRow, nullptr, 0, nPxl, nImg, rot, trans, pR, pT, score,
+                             cls, nPhaseOut, workspace, wsBytes, stream, true});
 }
 
 extern "C" int thx_expectation_ctf(const thx_expect_cfg* cfg, const thx_ctf_search_cfg* cs,
@@ -2675,7 +2682,7 @@ extern "C" int thx_expectation_ctf(const thx_expect_cfg* cfg, const thx_ctf_sear
                                    void* workspace, size_t wsBytes, thx_stream_t stream)
 {
     THX_CHECK_ARG(cs, "thx_expectation_ctf: null CTF-search configuration");
-    return expectation_impl(cfg, cs, vol, nullptr, nullptr, nullptr, nullptr, dat, nullptr,
-                            sigRcp, iCol, iRow, pxOrder, nOrd, nPxl, nImg, quat, trans, pR, pT,
-                            score, cls, nPhaseOut, workspace, wsBytes, stream);
+    return expectation_impl({cfg, cs, vol, nullptr, nullptr, nullptr, nullptr, dat, nullptr,
+                             sigRcp, iCol, iRow, pxOrder, nOrd, nPxl, nImg, quat, trans, pR, pT,
+                             score, cls, nPhaseOut, workspace, wsBytes, stream, false});
 }

@@ -14,7 +14,7 @@
 // image changes: every image's arithmetic is the same.
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "common.h"
+#include "internal.h"
 
 namespace {
 

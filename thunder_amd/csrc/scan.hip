@@ -4,7 +4,7 @@
 // (gpu/src/Kernel.cu:947-1004), dvp materialised in the workspace, then one
 // normalisation pass per image.  Kept as the arithmetic twin of the reference
 // and as the cross-check for the fused MFMA path (algo 1, scan_mfma.hip).
-#include "common.h"
+#include "internal.h"
 #include "scan_common.h"
 
 // --------------------------------------------------------------- a7 direct
@@ -130,22 +130,6 @@ __global__ void __launch_bounds__(256) k_weights_global(const float* __restrict_
     if (threadIdx.x == 0)
         wC[(size_t)l * nK + kIdx] = (float)(ssum[0] + ssum[1] + ssum[2] + ssum[3]);
 }
-
-namespace thx {
-int scan_mfma(const float* rotP, int nR, const float* traP, int nT,
-              const float* dat, const float* ctf, const float* sigRcp,
-              int nImg, int nPxl, const double* pR, const double* pT, int kIdx,
-              int nK, float* wC, float* wR, float* wT, float* baseL,
-              void* workspace, size_t wsBytes, hipStream_t stream);
-size_t scan_mfma_workspace(int nImg, int nR, int nT, int nPxl);
-int scan_split_algo(int algo, const float* rotP, int nR, const float* traP, int nT,
-                    const float* dat, const float* ctf, const float* sigRcp, int nImg, int nPxl,
-                    const double* pR, const double* pT, int kIdx, int nK, float* wC, float* wR,
-                    float* wT, float* baseL, float guard, float* dvpOut, void* workspace,
-                    size_t wsBytes, hipStream_t s);
-size_t scan_split_workspace(int nImg, int nR, int nT, int nPxl);
-float scan_guard_default();
-}  // namespace thx
 
 extern "C" size_t thx_global_scan_workspace(int nImg, int nR, int nT, int nPxl,
                                             int algo)

@@ -22,7 +22,7 @@
 // of all rotation blocks with exp(m_b - base) rescaling -- the same result as
 // the CPU online baseline (src/Optimiser.cpp:834-894) evaluated at its final
 // baseline.
-#include "common.h"
+#include "internal.h"
 #include "scan_common.h"
 
 namespace {

@@ -29,7 +29,7 @@
 // Epilogue: per-(image, rotation) max + wR marginal, then a block-local merge
 // of the 8 rotations into a (max, wT[NT_PAD]) partial per image;
 // k_scan_combine_bf folds the partials of all rotation blocks.
-#include "common.h"
+#include "internal.h"
 #include "scan_common.h"
 
 namespace {
@@ -926,12 +926,6 @@ int scan_split(const float* rotP, int nR, const float* traP, int nT, const float
 }  // namespace
 
 namespace thx {
-
-int scan_mfma(const float* rotP, int nR, const float* traP, int nT, const float* dat,
-              const float* ctf, const float* sigRcp, int nImg, int nPxl, const double* pR,
-              const double* pT, int kIdx, int nK, float* wC, float* wR, float* wT,
-              float* baseL, void* workspace, size_t wsBytes, hipStream_t stream);
-size_t scan_mfma_workspace(int nImg, int nR, int nT, int nPxl);
 
 // nT > 160: 2 x NF accumulators no longer fit one wave -- FP32 MFMA path (algo 1)
 size_t scan_split_workspace(int nImg, int nR, int nT, int nPxl)

@@ -31,7 +31,7 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "internal.h"
 #include "symmetry.h"
 
 namespace {

@@ -24,17 +24,7 @@
 //     F2D[nc] / T2D[nc] at R (iCol pf, iRow pf), O2D[nc] += -R (t - off),
 //     counter[nc] += 1.
 // 2D half-complex images: [vdim][vdim/2 + 1], i fastest, negative rows wrapped.
-#include "common.h"
-
-namespace thx {
-int launch_local_weights(const float* dvp, int nR, int nT, const double* pC, const double* pR,
-                         const double* pT, float* wC, float* wR, float* wT, float* baseL, int nImg,
-                         hipStream_t s, const int* act = nullptr, const int* nAct = nullptr);
-int launch_local_weights_d(const float* dvp, int nR, int nT, int nD, const double* pC,
-                           const double* pR, const double* pT, const double* pD, float* wC,
-                           float* wR, float* wT, float* wD, float* baseL, int nImg, hipStream_t s,
-                           const int* act = nullptr, const int* nAct = nullptr);
-}
+#include "internal.h"
 
 namespace {
 
@@ -282,8 +272,8 @@ int local_phase2d_launch(const float* vol, int vdim, int pf, const int* cls, con
                          const double* pR, const double* pT, const float* dat, const float* ctf,
                          const float* sigRcp, const int* iCol, const int* iRow, int nPxl, int idim,
                          int nImg, float* wC, float* wR, float* wT, float* baseL, float* dvp,
-                         const int* done, hipStream_t s, int nD = 0, const double* pD = nullptr,
-                         float* wD = nullptr, const int* act = nullptr, const int* nAct = nullptr)
+                         const int* done, hipStream_t s, int nD, const double* pD, float* wD,
+                         const int* act, const int* nAct)
 {
     // act / nAct (the driver's active list, with done): the weights of the
     // images still running only, as the 3D phase
