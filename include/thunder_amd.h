@@ -1008,6 +1008,78 @@ int thx_projectee2d(const float* src, int fromFT, int nK, int N, int pf, float r
                     const float* alphaMask, int interp, float scale, float* dst, void* workspace,
                     size_t wsBytes, thx_stream_t stream);
 
+/* ----------------------------------------------- signal subtraction ---
+ * The Subtract option after the last round (Optimiser::run,
+ * src/Optimiser.cpp:4163-4363): saveSubtract's per-image loop (:8418-8537)
+ * with the poses of saveDatabase's subtract branch (:8295-8361), on device
+ * (csrc/subtract.hip).  3D only: the reference aborts on Subtract in 2D mode
+ * (:8444-8450).  The pose comes from the caller, as in the noise model.
+ *
+ * thx_region_centroid -- centroid(const Volume&) (src/Image/ImageFunctions.cpp:
+ *   37-62) of a real map [N][N][N] (origin at index 0, negatives wrapped):
+ *   centre[3] (device, FP64) = sum (i, j, k) u / sum u with i, j, k in
+ *   [-N/2, N/2).  FP64 sums in a fixed-order tree, no atomics: bit-identical
+ *   from run to run.  As in the reference there is NO guard for a mask that
+ *   sums to zero: that gives inf / NaN.  N even, at most 4096.
+ * thx_region_centroid_workspace (host) -- the bytes it needs (the blocks'
+ *   partial sums); 0 for a bad N.
+ * thx_subtract -- vol: nK half-complex projectees of box vdim = pf idim (the
+ *   masked reference, thx_projectee with alphaMask); oriFT [nImg][idim]
+ *   [idim/2+1]: the unmasked originals (_imgOri); attr [nImg][8]; quat
+ *   [nImg][4], trans [nImg][2], offS [nImg][2] (NULL = 0), dF [nImg] (NULL =
+ *   1: the reference builds this CTF from the unscaled attributes, :8457-8466),
+ *   cls [nImg] (NULL = class 0); r = the projector's _maxRadius, 1 <= r <=
+ *   idim/2 - 1; symR [nSym][9] (device, FP64, row-major): the non-identity
+ *   elements in thx_symmetry's order, NULL with nSym 0; centre [3] (device,
+ *   FP64; NULL = 0): the region centre.  Per copy s in [0, nSym] and image l,
+ *   output plane s nImg + l (the reference's l + _ID.size() (i + 1)):
+ *     rotB = the matrix of quat[l]; rotC = rotB (s = 0), else symR[s-1]^T rotB
+ *       in FP64 (:8478-8488);
+ *     P = Projector::project(Image&, rot) (src/Projector.cpp:167-183): the
+ *       stored pixels j in [-r, r), i in [0, r] with i^2 + j^2 < r^2 -- not the
+ *       spectrum table's domain, which also drops rint|(i,j)| = r -- FP64
+ *       rotation -> FP32 coordinate, trilinear gather, 0 elsewhere; then
+ *       translate(P, r, t - offS) on the disc (:456-464; the shift / idim in
+ *       FP32, src/Image/ImageFunctions.cpp:322-339);
+ *     diff = ori - P ctf on every stored pixel (:8493-8500): pixels outside
+ *       the disc pass through;
+ *     diff *= exp(-2 pi i (i sx + j sy) / idim) with (sx, sy) = -t + offS -
+ *       (rotC^T centre).xy on every stored pixel, j in [-idim/2, idim/2), i in
+ *       [0, idim/2], Nyquist row and column included (:8502-8510,
+ *       ImageFunctions.cpp:269-284).
+ *   Outputs, each may be NULL but not all: diffFT [(1+nSym) nImg][idim]
+ *   [idim/2+1]; modelFT, same shape: P ctf after the first translate, before
+ *   the subtraction (what saveBestProjections renders); diffRL [(1+nSym) nImg]
+ *   [idim][idim]: the backward transform of diff scaled by 1 / idim^2
+ *   (FFT::bwExecutePlan, src/FFT.cpp:346-360), centred as in thx_img_stats (1:
+ *   the centred layout of an MRC stack; 0: the reference's corner origin); it
+ *   is transformed from a workspace copy, so diffFT survives, and needs
+ *   thx_subtract_workspace bytes; columns 0 and idim/2 of that copy are
+ *   replaced by their Hermitian part first, which is all FFTW's c2r reads of
+ *   them (the recentring phase leaves column idim/2 inconsistent), so the
+ *   result does not depend on how hipFFT reads such a column; quatOut [1+nSym]
+ *   [nImg][4] (FP64): quaternion(rotC) (src/Geometry/Euler.cpp:112-123), what
+ *   saveDatabase writes (:8311); shift [nImg][2] (FP64) = t - offS, what the
+ *   caller subtracts from the particle's translations (:8512-8517).
+ *   A class outside [0, nK) makes every output of that image NaN.  A gather
+ *   that would leave the projectee (a quaternion that is not a unit one) gives
+ *   a NaN pixel.  One workgroup per image, whatever nImg (the caller chunks
+ *   large stacks); stream-ordered, no host synchronisation, no atomics:
+ *   bit-identical from run to run.  Bad arguments are rejected before any
+ *   device work.
+ * thx_subtract_workspace (host) -- bytes for thx_subtract: the copy the C2R
+ *   consumes with wantRL, else 0; 0 for bad arguments. */
+size_t thx_region_centroid_workspace(int N);
+int thx_region_centroid(const float* map, int N, double* centre, void* workspace, size_t wsBytes,
+                        thx_stream_t stream);
+size_t thx_subtract_workspace(int nImg, int idim, int nSym, int wantRL);
+int thx_subtract(const float* vol, int vdim, int pf, int nK, const float* oriFT, const float* attr,
+                 const double* quat, const double* trans, const double* offS, const double* dF,
+                 const int* cls, int nImg, int idim, int r, const double* symR, int nSym,
+                 const double* centre, float* diffFT, float* modelFT, float* diffRL, int centred,
+                 double* quatOut, double* shift, void* workspace, size_t wsBytes,
+                 thx_stream_t stream);
+
 /* HIP event pairs for thx_expect_cfg.phaseEvents: create n (begin, end)
  * pairs, read back ms[i] per pair (-1: not recorded), destroy. */
 int thx_event_pairs_create(int n, void** events);
