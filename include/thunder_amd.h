@@ -865,6 +865,55 @@ int thx_pf_perturb2d(int nImg, int mR, int mT, double* rot, double* trans, doubl
                      double* pT, const double* k, const double* sd, double pf, double transS,
                      double transM, unsigned long long seed, unsigned stream_id,
                      thx_stream_t stream);
+/* The kernels that turn one phase of the 3D driver into the next, one launch
+ * each with the driver's grid shapes (all arrays device memory, nImg == 0 a
+ * no-op):
+ * thx_pf_perturb -- Particle::perturb + balanceWeight, 3D (src/Particle.cpp:
+ *   1149-1289): quat[l][i] <- mean[l] d conj(mean[l]) quat[l][i], d a normalised
+ *   N(0, diag(1, pf^2 min(1, k1), pf^2 min(1, k2), pf^2 min(1, k3))) (sampleACG,
+ *   DirectionalStat.cpp:39-91), then the symmetry counterpart nearest mean[l]
+ *   (symQuat nSym x 4, may be NULL with nSym = 0); trans += pf N(0, sd), re-drawn
+ *   as transS N(0, 1) beyond transM (reCentre, :2473-2495); pR / pT the
+ *   balanceWeight priors of the new clouds.  mean nImg x 4, k nImg x 3, sd
+ *   nImg x 2 (thx_pf_calvari); image l's lane j of 8 draws from the counter
+ *   stream (seed; l, stream_id, j).  done (may be NULL): images with done[l] != 0
+ *   are left untouched, priors included.
+ * thx_pf_class -- the class draw of the K > 1 reseed (src/Optimiser.cpp:
+ *   1933-1965): wC nImg x K class marginals (float), K in [1, 64], cls nImg.
+ * thx_pf_converge -- one phase of the stopping rule (src/Optimiser.cpp:
+ *   1510-1615) on k nImg x 3 / sd nImg x 2 of this phase's calVari: updates
+ *   bestR / bestT (/ bestD with sdD, both NULL without CTF search) and sets
+ *   done[l] = 1, nP[l] = phase where an image ends; images already done are
+ *   skipped.  twoD = 1: variR = k1.
+ * thx_pf_compact -- act[0 .. *nAct) = the images with done == 0 (done NULL:
+ *   all) in rising order, or in the order ord[nImg] lists them; act nImg ints.
+ * thx_pf_gather -- dst[l][j][:] = src[l][anc[l][j]][:] for j < nOut, rows of
+ *   `width` doubles, image l's source at src + l lds (lds = 0: one shared
+ *   source of nIn rows); anc values lie in [0, nIn).  done (may be NULL): done
+ *   images are skipped, or with keepDone = 1 (lds = nOut width, nIn = nOut)
+ *   copied unchanged.
+ * thx_pf_top_by_weight -- topQ[l] = quat[l][argmax_i pR[l][i]], the first on
+ *   ties (quat nImg x mR x 4, pR nImg x mR, topQ nImg x 4).
+ * thx_pf_top_copy -- topQ[l] = src[l][top[l]] (rows of 4 doubles, source
+ *   stride lds as in thx_pf_gather); done images (may be NULL) are skipped. */
+int thx_pf_perturb(int nImg, int mR, int mT, double* quat, double* trans, double* pR, double* pT,
+                   const double* mean, const double* k, const double* sd, double pf,
+                   double transS, double transM, unsigned long long seed, unsigned stream_id,
+                   const int* done, const double* symQuat, int nSym, thx_stream_t stream);
+int thx_pf_class(int nImg, int K, const float* wC, unsigned long long seed, unsigned stream_id,
+                 int* cls, thx_stream_t stream);
+int thx_pf_converge(int nImg, int phase, int minPhase, int lastPhase, const double* k,
+                    const double* sd, double* bestR, double* bestT, int* done, int* nP,
+                    const double* sdD, double* bestD, int twoD, thx_stream_t stream);
+int thx_pf_compact(int nImg, const int* done, const int* ord, int* act, int* nAct,
+                   thx_stream_t stream);
+int thx_pf_gather(int nImg, int nOut, int width, const double* src, long lds, int nIn,
+                  const int* anc, double* dst, const int* done, int keepDone,
+                  thx_stream_t stream);
+int thx_pf_top_by_weight(int nImg, int mR, const double* quat, const double* pR, double* topQ,
+                         thx_stream_t stream);
+int thx_pf_top_copy(int nImg, const double* src, long lds, const int* top, double* topQ,
+                    const int* done, thx_stream_t stream);
 
 /* ------------------------------------------------------- noise model ---
  * What Optimiser::maximization (src/Optimiser.cpp:3405-3559) does next to

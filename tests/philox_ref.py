@@ -37,6 +37,22 @@ def gauss(seed, a, b, c):
     return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
 
 
+def gauss2(seed, a, b, c, w=0):
+    """Philox::gauss2() of the draws w and w + 1 of the stream (a, b, c): both
+    branches of Box-Muller, (r cos, r sin) with r = sqrt(-2 ln u_w) and the
+    angle 2 pi u_{w+1}."""
+    w = np.asarray(w, np.uint64)
+    u1, u2 = uniform(seed, a, b, c, w), uniform(seed, a, b, c, w + np.uint64(1))
+    r = np.sqrt(-2.0 * np.log(u1))
+    return r * np.cos(2.0 * np.pi * u2), r * np.sin(2.0 * np.pi * u2)
+
+
+def word0(seed, a, b, c, w):
+    """Philox::next().x of draw w of the stream (a, b, c): the raw first word
+    (the integer draws of the shuffles: (x (i + 1)) >> 32)."""
+    return _philox_4x32_10(seed, a, b, c, w)[0]
+
+
 def mask_draws(seed, n_img, N):
     """The standard normals k_img_mask_scale draws for a stack [n_img, N, N]:
     pixel q (flat over the whole stack, corner-origin layout) owns the stream

@@ -208,6 +208,53 @@ def test_ctf_search_entry_points_validate_without_gpu(L):
     assert L.thx_global_sample_set(10, 1, 10.0, 1, dummy, dummy, dummy, dummy, None) == bad
 
 
+def test_pf_phase_entry_points_validate_without_gpu(L):
+    """The phase-to-phase kernels' entry points check their arguments before
+    any device work; empty batches are no-ops."""
+    ok, bad = 0, 1
+    d = ctypes.c_void_p(1)
+    perturb = lambda nImg, mR=9, mT=9, pf=1.0, q=d, sym=None, nSym=0: L.thx_pf_perturb(
+        nImg, mR, mT, q, d, d, d, d, d, d, pf, 10.0, 20.0, 1, 0, None, sym, nSym, None)
+    assert perturb(0, q=None) == ok
+    assert perturb(-1) == bad and perturb(4, mR=0) == bad and perturb(4, mT=0) == bad
+    assert perturb(4, pf=0.0) == bad and perturb(4, q=None) == bad
+    assert perturb(4, nSym=3) == bad and perturb(4, sym=d, nSym=-1) == bad
+    assert b"thx_pf_perturb" in L.thx_last_error()
+    # the class draw: K in [1, 64]
+    assert L.thx_pf_class(0, 4, None, 1, 999, None, None) == ok
+    assert L.thx_pf_class(4, 0, d, 1, 999, d, None) == bad
+    assert L.thx_pf_class(4, 65, d, 1, 999, d, None) == bad
+    assert L.thx_pf_class(4, 64, None, 1, 999, d, None) == bad
+    assert L.thx_pf_class(-1, 4, d, 1, 999, d, None) == bad
+    # the stopping rule: the defocus criterion's two arrays go together
+    conv = lambda nImg, sdD=None, bestD=None, twoD=0, k=d: L.thx_pf_converge(
+        nImg, 3, 2, 11, k, d, d, d, d, d, sdD, bestD, twoD, None)
+    assert conv(0, k=None) == ok
+    assert conv(-1) == bad and conv(4, k=None) == bad and conv(4, twoD=2) == bad
+    assert conv(4, sdD=d) == bad and conv(4, bestD=d) == bad
+    # the active list
+    assert L.thx_pf_compact(0, None, None, None, None, None) == ok
+    assert L.thx_pf_compact(-1, None, None, d, d, None) == bad
+    assert L.thx_pf_compact(4, None, None, None, d, None) == bad
+    assert L.thx_pf_compact(4, None, None, d, None, None) == bad
+    # the gather: a source stride of 0 or at least one image's rows; keepDone
+    # copies in place of the gather, so it needs the mask and equal layouts
+    gather = lambda nImg, nOut=9, width=2, lds=18, nIn=9, done=None, keep=0, src=d: \
+        L.thx_pf_gather(nImg, nOut, width, src, lds, nIn, d, d, done, keep, None)
+    assert gather(0, src=None) == ok
+    assert gather(-1) == bad and gather(4, nOut=0) == bad and gather(4, width=0) == bad
+    assert gather(4, nIn=0) == bad and gather(4, lds=17) == bad and gather(4, src=None) == bad
+    assert gather(4, keep=1) == bad and gather(4, done=d, keep=1, nIn=30, lds=60) == bad
+    assert gather(4, done=d, keep=1, lds=0) == bad
+    # the top particle
+    assert L.thx_pf_top_by_weight(0, 9, None, None, None, None) == ok
+    assert L.thx_pf_top_by_weight(4, 0, d, d, d, None) == bad
+    assert L.thx_pf_top_by_weight(4, 9, d, None, d, None) == bad
+    assert L.thx_pf_top_copy(0, None, 0, None, None, None, None) == ok
+    assert L.thx_pf_top_copy(4, d, -1, d, d, None, None) == bad
+    assert L.thx_pf_top_copy(4, d, 36, None, d, None, None) == bad
+
+
 def _policy(L, n, env=None, size=-1, rank=-1, cur=0):
     out = (ctypes.c_int * 16)()
     cnt = ctypes.c_int(0)

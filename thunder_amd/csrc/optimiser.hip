@@ -2002,6 +2002,104 @@ extern "C" int thx_pf_perturb2d(int nImg, int mR, int mT, double* rot, double* t
     return THX_OK;
 }
 
+// ---- the phase loop's small kernels one launch at a time, with the driver's
+// own grid shapes (Expect::reseed / perturb / resample_phase / run)
+
+extern "C" int thx_pf_perturb(int nImg, int mR, int mT, double* quat, double* trans, double* pR,
+                              double* pT, const double* mean, const double* k, const double* sd,
+                              double pf, double transS, double transM, unsigned long long seed,
+                              unsigned stream_id, const int* done, const double* symQuat,
+                              int nSym, thx_stream_t stream)
+{
+    THX_CHECK_ARG(nImg >= 0 && mR > 0 && mT > 0 && pf > 0.0 && nSym >= 0,
+                  "thx_pf_perturb: bad arguments");
+    THX_CHECK_ARG(nImg == 0 || (quat && trans && pR && pT && mean && k && sd),
+                  "thx_pf_perturb: null argument");
+    THX_CHECK_ARG(nSym == 0 || symQuat, "thx_pf_perturb: nSym without symQuat");
+    if (nImg == 0) return THX_OK;
+    // the rotation mean is one pointer: meanMode 0 reads it as topQ
+    THX_LAUNCH(k_pf_perturb, dim3(thx::cdiv(nImg * GROUP, 256)), dim3(256), 0,
+               thx::as_stream(stream), nImg, mR, mT, quat, trans, pR, pT, mean, k, sd, pf, transS,
+               transM, (uint64_t)seed, (uint32_t)stream_id, 0, nullptr, done, symQuat, nSym);
+    return THX_OK;
+}
+
+extern "C" int thx_pf_class(int nImg, int K, const float* wC, unsigned long long seed,
+                            unsigned stream_id, int* cls, thx_stream_t stream)
+{
+    THX_CHECK_ARG(nImg >= 0 && K >= 1 && K <= KMAX_CLASS, "thx_pf_class: bad sizes (K in [1, 64])");
+    THX_CHECK_ARG(nImg == 0 || (wC && cls), "thx_pf_class: null argument");
+    if (nImg == 0) return THX_OK;
+    THX_LAUNCH(k_pf_class, dim3(thx::cdiv(nImg, 256)), dim3(256), 0, thx::as_stream(stream), nImg,
+               K, wC, (uint64_t)seed, (uint32_t)stream_id, cls);
+    return THX_OK;
+}
+
+extern "C" int thx_pf_converge(int nImg, int phase, int minPhase, int lastPhase, const double* k,
+                               const double* sd, double* bestR, double* bestT, int* done, int* nP,
+                               const double* sdD, double* bestD, int twoD, thx_stream_t stream)
+{
+    THX_CHECK_ARG(nImg >= 0 && phase >= 0 && (twoD == 0 || twoD == 1),
+                  "thx_pf_converge: bad arguments");
+    THX_CHECK_ARG(nImg == 0 || (k && sd && bestR && bestT && done && nP),
+                  "thx_pf_converge: null argument");
+    THX_CHECK_ARG(!sdD == !bestD, "thx_pf_converge: sdD and bestD go together");
+    if (nImg == 0) return THX_OK;
+    THX_LAUNCH(k_pf_converge, dim3(thx::cdiv(nImg, 256)), dim3(256), 0, thx::as_stream(stream),
+               nImg, phase, minPhase, lastPhase, k, sd, bestR, bestT, done, nP, sdD, bestD, twoD);
+    return THX_OK;
+}
+
+extern "C" int thx_pf_compact(int nImg, const int* done, const int* ord, int* act, int* nAct,
+                              thx_stream_t stream)
+{
+    THX_CHECK_ARG(nImg >= 0, "thx_pf_compact: bad sizes");
+    THX_CHECK_ARG(nImg == 0 || (act && nAct), "thx_pf_compact: null argument");
+    if (nImg == 0) return THX_OK;
+    THX_LAUNCH(k_compact, dim3(1), dim3(1024), 0, thx::as_stream(stream), nImg, done, act, nAct,
+               ord);
+    return THX_OK;
+}
+
+extern "C" int thx_pf_gather(int nImg, int nOut, int width, const double* src, long lds, int nIn,
+                             const int* anc, double* dst, const int* done, int keepDone,
+                             thx_stream_t stream)
+{
+    THX_CHECK_ARG(nImg >= 0 && nOut > 0 && width > 0 && nIn > 0 &&
+                      (lds == 0 || lds >= (long)nIn * width),
+                  "thx_pf_gather: bad sizes");
+    // keepDone copies src[q] at dst's own index: the two share one layout
+    THX_CHECK_ARG(!keepDone || (done && nIn == nOut && lds == (long)nOut * width),
+                  "thx_pf_gather: keepDone needs done and lds = nOut * width, nIn = nOut");
+    THX_CHECK_ARG(nImg == 0 || (src && anc && dst), "thx_pf_gather: null argument");
+    if (nImg == 0) return THX_OK;
+    THX_LAUNCH(k_gather, dim3(1024), dim3(256), 0, thx::as_stream(stream), nImg, nOut, width, src,
+               lds, nIn, anc, dst, done, keepDone);
+    return THX_OK;
+}
+
+extern "C" int thx_pf_top_by_weight(int nImg, int mR, const double* quat, const double* pR,
+                                    double* topQ, thx_stream_t stream)
+{
+    THX_CHECK_ARG(nImg >= 0 && mR > 0, "thx_pf_top_by_weight: bad sizes");
+    THX_CHECK_ARG(nImg == 0 || (quat && pR && topQ), "thx_pf_top_by_weight: null argument");
+    if (nImg == 0) return THX_OK;
+    THX_LAUNCH(k_top_by_weight, dim3(thx::cdiv(nImg, 256)), dim3(256), 0, thx::as_stream(stream),
+               nImg, mR, quat, pR, topQ);
+    return THX_OK;
+}
+
+extern "C" int thx_pf_top_copy(int nImg, const double* src, long lds, const int* top, double* topQ,
+                               const int* done, thx_stream_t stream)
+{
+    THX_CHECK_ARG(nImg >= 0 && lds >= 0, "thx_pf_top_copy: bad sizes");
+    THX_CHECK_ARG(nImg == 0 || (src && top && topQ), "thx_pf_top_copy: null argument");
+    if (nImg == 0) return THX_OK;
+    THX_LAUNCH(k_top_copy, dim3(thx::cdiv(4 * nImg, 256)), dim3(256), 0, thx::as_stream(stream),
+               nImg, src, lds, top, topQ, done);
+    return THX_OK;
+}
+
 extern "C" int thx_pf_defocus(int nImg, int mD, int op, double arg, unsigned long long seed,
                               unsigned stream_id, double* d, double* pD, double* sd,
                               thx_stream_t stream)

@@ -970,3 +970,121 @@ def pf_peak(u, peak=None):
     check(lib().thx_pf_peak(nImg, n, _ptr(u), n, _ptr(peak), int(set_factor), _stream(u.device)),
           "thx_pf_peak")
     return u, peak
+
+
+# ------------------------------------------ the phase loop's small kernels
+def _opt(t, dtype, shape, name):
+    return None if t is None else _req(t, dtype, shape, name)
+
+
+def pf_perturb(quat, trans, mean, k, sd, pf, trans_s, trans_m, seed, stream_id=0, done=None,
+               symQ=None, pR=None, pT=None):
+    """thx_pf_perturb: Particle::perturb + balanceWeight of the 3D clouds quat
+    [nImg, mR, 4] / trans [nImg, mT, 2] in place, about the rotation means
+    mean [nImg, 4] with the spreads k [nImg, 3] / sd [nImg, 2]; returns the
+    priors (pR [nImg, mR], pT [nImg, mT]).  done [nImg] int32: images left
+    untouched (pass pR / pT to see that); symQ: symmetry elements [n, 4]."""
+    nImg, mR = quat.shape[:2]
+    mT = trans.shape[1]
+    dev = quat.device
+    _req(quat, torch.float64, (nImg, mR, 4), "quat")
+    _req(trans, torch.float64, (nImg, mT, 2), "trans")
+    _req(mean, torch.float64, (nImg, 4), "mean")
+    _req(k, torch.float64, (nImg, 3), "k")
+    _req(sd, torch.float64, (nImg, 2), "sd")
+    _opt(done, torch.int32, (nImg,), "done")
+    pR = torch.empty(nImg, mR, dtype=torch.float64, device=dev) if pR is None else \
+        _req(pR, torch.float64, (nImg, mR), "pR")
+    pT = torch.empty(nImg, mT, dtype=torch.float64, device=dev) if pT is None else \
+        _req(pT, torch.float64, (nImg, mT), "pT")
+    Q = None
+    if symQ is not None and len(symQ):
+        Q = torch.as_tensor(np.ascontiguousarray(symQ, np.float64), device=dev).reshape(-1, 4)
+    check(lib().thx_pf_perturb(nImg, mR, mT, _ptr(quat), _ptr(trans), _ptr(pR), _ptr(pT),
+                               _ptr(mean), _ptr(k), _ptr(sd), float(pf), float(trans_s),
+                               float(trans_m), int(seed), int(stream_id), _ptr(done), _ptr(Q),
+                               0 if Q is None else Q.shape[0], _stream(dev)), "thx_pf_perturb")
+    return pR, pT
+
+
+def pf_class(wC, seed, stream_id=0):
+    """thx_pf_class: the reseed's class draw from marginals wC [nImg, K] float32."""
+    nImg, K = wC.shape
+    _req(wC, torch.float32, (nImg, K), "wC")
+    cls = torch.empty(nImg, dtype=torch.int32, device=wC.device)
+    check(lib().thx_pf_class(nImg, K, _ptr(wC), int(seed), int(stream_id), _ptr(cls),
+                             _stream(wC.device)), "thx_pf_class")
+    return cls
+
+
+def pf_converge(phase, min_phase, last_phase, k, sd, bestR, bestT, done, nP, sdD=None, bestD=None,
+                two_d=False):
+    """thx_pf_converge: one phase of the stopping rule, updating bestR / bestT
+    (/ bestD) [nImg] float64 and done / nP [nImg] int32 in place."""
+    nImg = k.shape[0]
+    _req(k, torch.float64, (nImg, 3), "k")
+    _req(sd, torch.float64, (nImg, 2), "sd")
+    _req(bestR, torch.float64, (nImg,), "bestR")
+    _req(bestT, torch.float64, (nImg,), "bestT")
+    _req(done, torch.int32, (nImg,), "done")
+    _req(nP, torch.int32, (nImg,), "nP")
+    _opt(sdD, torch.float64, (nImg,), "sdD")
+    _opt(bestD, torch.float64, (nImg,), "bestD")
+    check(lib().thx_pf_converge(nImg, int(phase), int(min_phase), int(last_phase), _ptr(k),
+                                _ptr(sd), _ptr(bestR), _ptr(bestT), _ptr(done), _ptr(nP),
+                                _ptr(sdD), _ptr(bestD), int(bool(two_d)), _stream(k.device)),
+          "thx_pf_converge")
+
+
+def pf_compact(n_img, device, done=None, order=None):
+    """thx_pf_compact: (act [n_img] int32, nAct [1] int32); act[:nAct] lists the
+    images with done == 0, rising or in the order `order` [n_img] gives."""
+    _opt(done, torch.int32, (n_img,), "done")
+    _opt(order, torch.int32, (n_img,), "order")
+    act = torch.full((n_img,), -1, dtype=torch.int32, device=device)
+    n_act = torch.zeros(1, dtype=torch.int32, device=device)
+    check(lib().thx_pf_compact(n_img, _ptr(done), _ptr(order), _ptr(act), _ptr(n_act),
+                               _stream(act.device)), "thx_pf_compact")
+    return act, n_act
+
+
+def pf_gather(src, anc, dst, n_in, done=None, keep_done=False):
+    """thx_pf_gather into dst [nImg, nOut, width] from src [nImg, n_in, width]
+    (or [n_in, width], one source shared by all images) by ancestors anc
+    [nImg, nOut] int32 with values in [0, n_in)."""
+    nImg, nOut, width = dst.shape
+    shared = src.dim() == 2
+    _req(dst, torch.float64, (nImg, nOut, width), "dst")
+    _req(src, torch.float64, (n_in, width) if shared else (nImg, n_in, width), "src")
+    _req(anc, torch.int32, (nImg, nOut), "anc")
+    _opt(done, torch.int32, (nImg,), "done")
+    check(lib().thx_pf_gather(nImg, nOut, width, _ptr(src), 0 if shared else n_in * width, n_in,
+                              _ptr(anc), _ptr(dst), _ptr(done), int(bool(keep_done)),
+                              _stream(dst.device)), "thx_pf_gather")
+    return dst
+
+
+def pf_top_by_weight(quat, pR):
+    """thx_pf_top_by_weight: the particle of largest prior per image [nImg, 4]."""
+    nImg, mR = quat.shape[:2]
+    _req(quat, torch.float64, (nImg, mR, 4), "quat")
+    _req(pR, torch.float64, (nImg, mR), "pR")
+    top = torch.empty(nImg, 4, dtype=torch.float64, device=quat.device)
+    check(lib().thx_pf_top_by_weight(nImg, mR, _ptr(quat), _ptr(pR), _ptr(top),
+                                     _stream(quat.device)), "thx_pf_top_by_weight")
+    return top
+
+
+def pf_top_copy(src, top, topQ, done=None):
+    """thx_pf_top_copy: topQ[l] = src[l][top[l]] (src [nImg, n, 4] or a shared
+    [n, 4]; top [nImg] int32 with values in [0, n)); done images are skipped."""
+    nImg = topQ.shape[0]
+    shared = src.dim() == 2
+    n = src.shape[-2]
+    _req(src, torch.float64, (n, 4) if shared else (nImg, n, 4), "src")
+    _req(top, torch.int32, (nImg,), "top")
+    _req(topQ, torch.float64, (nImg, 4), "topQ")
+    _opt(done, torch.int32, (nImg,), "done")
+    check(lib().thx_pf_top_copy(nImg, _ptr(src), 0 if shared else n * 4, _ptr(top), _ptr(topQ),
+                                _ptr(done), _stream(topQ.device)), "thx_pf_top_copy")
+    return topQ
