@@ -618,6 +618,18 @@ int thx_reconstruct(const float* F, float* T, int N, int pf, float a, float alph
                     int joinHalf, float* dst, float* dstFT, int* nIter, float* diffOut,
                     void* workspace, size_t wsBytes, thx_stream_t stream);
 
+/* The balanced weights of that solve alone (for tests and diagnosis): the
+ * same host sequence as thx_reconstruct up to the pad -- MAP factor, W / T
+ * init, the balancing loop or W = 1 / max(|T|, 1e-6) -- with T modified in
+ * place in the same way, and W [vdim][vdim][vdim/2+1] float (device) copied
+ * out.  method 0: the solve's own choice of balancing loop, 1: two 3D
+ * transforms per iteration, 2: the even half-grid loop (THX_ERR_ARG where it
+ * has no transforms: vdim other than 64, 128, 256, 512).  Same workspace. */
+int thx_reconstruct_weights(float* T, int N, int pf, float a, float alpha, int gridCorr,
+                            int maxRadius, int map, const double* fsc, int nFsc, int joinHalf,
+                            int method, float* W, int* nIter, float* diffOut,
+                            void* workspace, size_t wsBytes, thx_stream_t stream);
+
 /* MODE_2D: the 2D branches of Reconstructor::reconstruct (src/Reconstructor.cpp:
  * 1136-1589, 1669-1818; GPU ExposePT2D / ExposeWT2D / ExposePF2D /
  * ExposeCorrF2D) for nK class images at once, each with its own balancing

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import recon_ref
 from oracle import reconstruct as orc_rc
 from stacks import small_stack
 from thunder_amd import ops, synth
@@ -95,16 +96,18 @@ def test_halfmap_fsc_end_to_end(orc):
     assert np.max(rel[1:]) < 1e-4, rel
 
 
-@pytest.mark.parametrize("vdim", [64, 128, 512])
+@pytest.mark.parametrize("vdim", [16, 32, 64, 128, 256, 512])
 def test_fft3d_column_passes_match_numpy_and_hipfft(vdim):
     """thx_fft3d: the LDS column passes (method 2) against numpy's rfftn /
     irfftn (float64) and against hipFFT's 3D plans (method 1) on the same
-    input, both directions (FFT::fw / FFT::bw conventions: unnormalised)."""
+    input, both directions (FFT::fw / FFT::bw conventions: unnormalised).
+    16 and 32 are the smallest boxes with column passes: their last column
+    tiles hold 9 and 1 columns, and half the threads idle in the sweeps."""
     import ctypes
     from thunder_amd._lib import check, lib
     rng = np.random.default_rng(vdim)
     x = rng.standard_normal((vdim, vdim, vdim)).astype(np.float32)
-    X = np.fft.rfftn(x.astype(np.float64)) if vdim <= 128 else None
+    X = np.fft.rfftn(x.astype(np.float64)) if vdim <= 256 else None
     ws = ops.workspace(lib().thx_fft3d_workspace(vdim), DEV)
     out = {}
     for method in (1, 2):
@@ -128,60 +131,6 @@ def test_fft3d_column_passes_match_numpy_and_hipfft(vdim):
     assert np.max(np.abs(out[(2, "bw")] - out[(1, "bw")])) <= 2e-6 * np.abs(out[(1, "bw")]).max()
 
 
-def _reconstruct_f64_torch(F, T, N, pf, a=1.9, alpha=15.0):
-    """oracle/reconstruct.py's reconstruct (grid correction, no MAP) restated
-    line for line in float64 torch on the GPU, so the restatement runs at the
-    bench's 512^3 padded box in seconds (torch's double-precision FFTs; the
-    kernel table from the oracle's MKB closed forms)."""
-    vdim = pf * N
-    dev = F.device
-    maxR = N // 2 - int(np.ceil(a))
-    i = torch.arange(vdim // 2 + 1, device=dev, dtype=torch.float64)
-    j = torch.fft.fftfreq(vdim, 1.0 / vdim, device=dev, dtype=torch.float64)
-    quad = j[:, None, None] ** 2 + j[None, :, None] ** 2 + i[None, None, :] ** 2
-    inside = quad < (maxR * pf) ** 2
-    del quad
-    T = torch.clamp(T.double(), min=1e-25)
-    W = inside.double()
-    tab = torch.as_tensor(orc_rc.mkb_rl_r2(np.arange(orc_rc.TAB_N + 1) * 1e-5, a, alpha)
-                          .astype(np.float32).astype(np.float64), device=dev)
-    nf = float(orc_rc.mkb_rl_r2(np.array([0.0]), a, alpha)[0])
-    c = torch.fft.fftfreq(vdim, 1.0 / vdim, device=dev, dtype=torch.float64)
-    rq = c[:, None, None] ** 2 + c[None, :, None] ** 2 + c[None, None, :] ** 2
-    idx = torch.clamp(torch.round((rq / float(vdim * vdim)) / 1e-5).long(), max=orc_rc.TAB_N)
-    kern = tab[idx] / nf
-    del rq, idx
-    diff_prev = diff = float(np.finfo(np.float32).max)
-    n_no, m = 0, 0
-    for m in range(30):
-        C = T * W
-        cr = torch.fft.irfftn(C.to(torch.complex128), s=(vdim, vdim, vdim)) * kern
-        C = torch.fft.rfftn(cr)
-        del cr
-        a_ = C.abs()
-        del C
-        W = torch.where(inside, W / torch.clamp(a_, min=1e-6), W)
-        diff_prev, diff = diff, float((a_[inside] - 1).abs().max())
-        del a_
-        n_no = n_no + 1 if diff > diff_prev * 0.95 else 0
-        if diff < 1e-2 or (m >= 10 and n_no == 2):
-            m += 1
-            break
-    else:
-        m = 30
-    pad = torch.where(inside, F.to(torch.complex128) * W, torch.zeros((), dtype=torch.complex128,
-                                                                        device=dev))
-    rl = torch.fft.irfftn(pad, s=(vdim, vdim, vdim))
-    del pad
-    cN = torch.fft.fftfreq(N, 1.0 / N, device=dev).long() % vdim
-    box = rl[cN][:, cN][:, :, cN]
-    cc = torch.fft.fftfreq(N, 1.0 / N, device=dev, dtype=torch.float64)
-    r = torch.sqrt(cc[:, None, None] ** 2 + cc[None, :, None] ** 2 + cc[None, None, :] ** 2) / vdim
-    x = np.pi * r
-    j0 = torch.where(x == 0, torch.ones_like(x), torch.sin(x) / torch.where(x == 0, torch.ones_like(x), x))
-    return (box / (j0 * j0)).cpu().numpy(), m
-
-
 def test_reconstruct_at_the_bench_box_matches_f64():
     """The bench's solve (box 256, 512^3 padded -- the even half-grid
     balancing) against the float64 restatement at the same size: map within
@@ -197,7 +146,8 @@ def test_reconstruct_at_the_bench_box_matches_f64():
     del quad
     F = vol * T
     del vol
-    ref, rit = _reconstruct_f64_torch(F, T, N, pf)
+    ref, _, _, rit, _ = recon_ref.reconstruct(F, T, N, pf)
+    ref = ref.cpu().numpy()
     hm = ops.HalfMap(vdim, DEV)
     hm.F.copy_(F)
     hm.T.copy_(T)

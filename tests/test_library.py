@@ -161,6 +161,30 @@ def test_round2_entry_points_validate_without_gpu(L):
     assert L.thx_halfmap_allreduce(None, None, None, None, None, 10, 1, None) == bad
 
 
+def test_reconstruct_weights_validates_without_gpu(L):
+    """thx_reconstruct_weights checks its arguments before any device work:
+    null T / W, odd N, bad pf / a / alpha, a method outside 0..2, MAP without
+    the FSC, a maxRadius past N/2, and method 2 (the even half-grid loop)
+    at a padded box it has no transforms for -- with a message that says so."""
+    d = ctypes.c_void_p(16)
+    call = lambda T=d, W=d, N=16, pf=2, a=1.9, alpha=15.0, maxRadius=0, map_=0, fsc=None, nFsc=0, \
+        method=0: L.thx_reconstruct_weights(T, N, pf, a, alpha, 1, maxRadius, map_, fsc, nFsc, 0,
+                                            method, W, None, None, None, 0, None)
+    assert call(T=None) == 1 and call(W=None) == 1
+    assert call(N=0) == 1 and call(N=15) == 1 and call(pf=0) == 1
+    assert call(a=0.0) == 1 and call(alpha=0.0) == 1
+    assert call(method=-1) == 1 and call(method=3) == 1
+    assert b"thx_reconstruct_weights" in L.thx_last_error()
+    assert call(map_=1) == 1 and call(map_=1, fsc=d, nFsc=0) == 1
+    assert b"FSC" in L.thx_last_error()
+    assert call(maxRadius=9) == 1
+    assert b"maxRadius" in L.thx_last_error()
+    for N, pf in ((16, 2), (20, 2), (16, 3), (200, 2), (512, 2)):    # vdim 32, 40, 48, 400, 1024
+        assert call(N=N, pf=pf, method=2) == 1
+        assert b"even half-grid" in L.thx_last_error()
+        assert str(N * pf).encode() in L.thx_last_error()
+
+
 def test_global_sample_sizes_match_survey():
     """a3 sizes (host function, no GPU): nT = 151 at transS 10, tsf 0.25
     (SURVEY 8a), the 3D clamp 500 -> 1500 (C2), nR = mS / (1 + nSym)."""

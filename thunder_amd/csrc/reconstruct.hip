@@ -845,33 +845,34 @@ extern "C" size_t thx_reconstruct_workspace(int N, int pf)
     return k.off + 256;
 }
 
-extern "C" int thx_reconstruct(const float* F, float* T, int N, int pf, float a, float alpha,
-                               int gridCorr, int maxRadius, int map, const double* fsc, int nFsc,
-                               int joinHalf, float* dst, float* dstFT, int* nIter, float* diffOut,
-                               void* workspace, size_t wsBytes, thx_stream_t stream)
+namespace {
+
+// what the pad needs of a solve's workspace (carved in thx_reconstruct_workspace's order)
+struct SolveBufs {
+    float* W;
+    float2* C;
+    float* rl;
+};
+
+// The solve up to its weights, shared by thx_reconstruct and
+// thx_reconstruct_weights: the workspace carved and the plans of pe (locked
+// by the caller) bound to it and to s, then the MAP factor, W / T init and
+// the balancing loop (or W = 1 / max(|T|, 1e-6)).  method 0: the even
+// half-grid loop where its transforms exist, else two 3D transforms per
+// iteration; 1 / 2 force the one or the other.
+int solve_weights(PlanEntry* pe, float* T, int N, int pf, float a, float alpha, int gridCorr,
+                  int maxR, int map, const double* fsc, int nFsc, int joinHalf, int method,
+                  bool wantFT, int* nIter, float* diffOut, void* workspace, size_t wsBytes,
+                  hipStream_t s, SolveBufs& b)
 {
-    THX_CHECK_ARG(F && T && dst && N > 0 && N % 2 == 0 && pf > 0 && a > 0 && alpha > 0,
-                  "thx_reconstruct: bad arguments");
-    THX_CHECK_ARG(!map || (fsc && nFsc > 0), "thx_reconstruct: MAP needs the FSC");
     const int vdim = N * pf;
-    const int maxR = maxRadius > 0 ? maxRadius : N / 2 - (int)std::ceil(a);   // Reconstructor::init
-    THX_CHECK_ARG(maxR > 0 && maxR <= N / 2, "thx_reconstruct: bad maxRadius");
-    const size_t need = thx_reconstruct_workspace(N, pf);
-    THX_CHECK_ARG(need > 0 && workspace && wsBytes >= need, "thx_reconstruct: workspace too small");
-    hipStream_t s = thx::as_stream(stream);
-    std::unique_lock<std::mutex> lk;     // this stream's plans, held for the solve
-    PlanEntry* pe = nullptr;
-    {
-        const int st = cached_plans(vdim, N, s, &pe, lk);
-        if (st != THX_OK) return st;
-    }
     Plans& pl = pe->p;
     const size_t work = pl.work;
     const size_t dimSize = (size_t)(vdim / 2 + 1) * vdim * vdim;
     thx::Carver k(workspace, wsBytes);
-    float* W = k.take<float>(dimSize);
-    float2* C = k.take<float2>(dimSize);
-    float* rl = k.take<float>((size_t)vdim * vdim * vdim);
+    float* W = b.W = k.take<float>(dimSize);
+    float2* C = b.C = k.take<float2>(dimSize);
+    float* rl = b.rl = k.take<float>((size_t)vdim * vdim * vdim);
     float* tab = k.take<float>(TAB_N + 1);
     float* oct = k.take<float>((size_t)(vdim / 2 + 1) * (vdim / 2 + 1) * (vdim / 2 + 1));
     unsigned* diff = k.take<unsigned>(64);
@@ -886,7 +887,7 @@ extern "C" int thx_reconstruct(const float* F, float* T, int N, int pf, float a,
         THX_FFT(hipfftSetStream(pl.c2rX, s));
         THX_FFT(hipfftSetStream(pl.r2cX, s));
     }
-    if (dstFT) {
+    if (wantFT) {
         THX_FFT(hipfftSetWorkArea(pl.r2cN, fftWork));
         THX_FFT(hipfftSetStream(pl.r2cN, s));
     }
@@ -898,12 +899,12 @@ extern "C" int thx_reconstruct(const float* F, float* T, int N, int pf, float a,
     const long r2 = (long)maxR * pf * maxR * pf;
     const long nFT = (long)dimSize;
     const float scaleBw = 1.f / ((float)vdim * vdim * vdim);
-    const dim3 g(4096), b(256);
+    const dim3 g(4096), blk(256);
     if (map) {
-        hipLaunchKernelGGL(k_wiener, g, b, 0, s, T, vdim, pf, maxR, fsc, nFsc, joinHalf);
+        hipLaunchKernelGGL(k_wiener, g, blk, 0, s, T, vdim, pf, maxR, fsc, nFsc, joinHalf);
         THX_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_init_w, g, b, 0, s, W, T, vdim, r2);
+    hipLaunchKernelGGL(k_init_w, g, blk, 0, s, W, T, vdim, r2);
     THX_LAUNCH_CHECK();
     int m = 0;
     float diffC = 0.f;
@@ -913,17 +914,18 @@ extern "C" int thx_reconstruct(const float* F, float* T, int N, int pf, float a,
         int nNoDec = 0;
         const dim3 gSlab(RB_SPLIT, vdim), bSlab(RB_THREADS);
         const unsigned mVdim = magic_u((unsigned)vdim), mNc = magic_u((unsigned)(vdim / 2 + 1));
-        hipLaunchKernelGGL(k_kernel_octant, g, b, 0, s, oct, vdim, tab, nf, scaleBw);
+        hipLaunchKernelGGL(k_kernel_octant, g, blk, 0, s, oct, vdim, tab, nf, scaleBw);
         THX_LAUNCH_CHECK();
         // the even half-grid loop where its transforms exist, else two hipFFT
         // 3D transforms per iteration
-        const bool even = even_ok(vdim) && pl.tw;
+        const bool even = method != 1 && even_ok(vdim) && pl.tw;
+        THX_CHECK_ARG(even || method != 2, "thx_reconstruct_weights: no even half-grid loop for vdim %d", vdim);
         if (even) {
-            hipLaunchKernelGGL(k_sym_planes, g, b, 0, s, T, vdim);
+            hipLaunchKernelGGL(k_sym_planes, g, blk, 0, s, T, vdim);
             THX_LAUNCH_CHECK();
             THX_RET(even_iteration(vdim, C, W, T, oct, r2, diff, pl.tw, true, false, s));
         } else {
-            hipLaunchKernelGGL(k_c_from_tw, g, b, 0, s, C, T, W, nFT);
+            hipLaunchKernelGGL(k_c_from_tw, g, blk, 0, s, C, T, W, nFT);
             THX_LAUNCH_CHECK();
         }
         unsigned* bits = pe->bits;   // the entry's pinned word (no allocation per solve)
@@ -954,21 +956,88 @@ extern "C" int thx_reconstruct(const float* F, float* T, int N, int pf, float a,
             }
         }
     } else {
-        hipLaunchKernelGGL(k_w_from_t, g, b, 0, s, W, T, vdim, r2);
+        hipLaunchKernelGGL(k_w_from_t, g, blk, 0, s, W, T, vdim, r2);
         THX_LAUNCH_CHECK();
     }
     if (nIter) *nIter = m;
+    return THX_OK;
+}
+
+}  // namespace
+
+extern "C" int thx_reconstruct(const float* F, float* T, int N, int pf, float a, float alpha,
+                               int gridCorr, int maxRadius, int map, const double* fsc, int nFsc,
+                               int joinHalf, float* dst, float* dstFT, int* nIter, float* diffOut,
+                               void* workspace, size_t wsBytes, thx_stream_t stream)
+{
+    THX_CHECK_ARG(F && T && dst && N > 0 && N % 2 == 0 && pf > 0 && a > 0 && alpha > 0,
+                  "thx_reconstruct: bad arguments");
+    THX_CHECK_ARG(!map || (fsc && nFsc > 0), "thx_reconstruct: MAP needs the FSC");
+    const int vdim = N * pf;
+    const int maxR = maxRadius > 0 ? maxRadius : N / 2 - (int)std::ceil(a);   // Reconstructor::init
+    THX_CHECK_ARG(maxR > 0 && maxR <= N / 2, "thx_reconstruct: bad maxRadius");
+    const size_t need = thx_reconstruct_workspace(N, pf);
+    THX_CHECK_ARG(need > 0 && workspace && wsBytes >= need, "thx_reconstruct: workspace too small");
+    hipStream_t s = thx::as_stream(stream);
+    std::unique_lock<std::mutex> lk;     // this stream's plans, held for the solve
+    PlanEntry* pe = nullptr;
+    {
+        const int st = cached_plans(vdim, N, s, &pe, lk);
+        if (st != THX_OK) return st;
+    }
+    Plans& pl = pe->p;
+    SolveBufs b;
+    THX_RET(solve_weights(pe, T, N, pf, a, alpha, gridCorr, maxR, map, fsc, nFsc, joinHalf, 0,
+                          dstFT != nullptr, nIter, diffOut, workspace, wsBytes, s, b));
+    const long r2 = (long)maxR * pf * maxR * pf;
+    const float scaleBw = 1.f / ((float)vdim * vdim * vdim);
+    const dim3 g(4096), blk(256);
     // F W -> real space -> central box, kernel-corrected
-    hipLaunchKernelGGL(k_pad, g, b, 0, s, C, reinterpret_cast<const float2*>(F), W, vdim, r2);
+    hipLaunchKernelGGL(k_pad, g, blk, 0, s, b.C, reinterpret_cast<const float2*>(F), b.W, vdim, r2);
     THX_LAUNCH_CHECK();
-    THX_RET(c2r3d(pl, C, rl, vdim, s));
-    hipLaunchKernelGGL(k_extract, g, b, 0, s, dst, rl, N, vdim, scaleBw);
+    THX_RET(c2r3d(pl, b.C, b.rl, vdim, s));
+    hipLaunchKernelGGL(k_extract, g, blk, 0, s, dst, b.rl, N, vdim, scaleBw);
     THX_LAUNCH_CHECK();
     if (dstFT) {
         // the map's transform for the FSC (fft.fw(ref), src/Optimiser.cpp:7379)
         THX_FFT(hipfftExecR2C(pl.r2cN, dst, reinterpret_cast<hipfftComplex*>(dstFT)));
     }
     // the plans are shared: finish before another call rebinds their stream
+    THX_HIP(hipStreamSynchronize(s));
+    return THX_OK;
+}
+
+// The balanced weights of thx_reconstruct's solve alone: the same host
+// sequence up to the pad (T modified in place in the same way), W copied out.
+// method 0: the solve's own choice of balancing loop, 1: the 3D-transform
+// loop, 2: the even half-grid loop (error where it has no transforms).
+extern "C" int thx_reconstruct_weights(float* T, int N, int pf, float a, float alpha, int gridCorr,
+                                       int maxRadius, int map, const double* fsc, int nFsc,
+                                       int joinHalf, int method, float* W, int* nIter,
+                                       float* diffOut, void* workspace, size_t wsBytes,
+                                       thx_stream_t stream)
+{
+    THX_CHECK_ARG(T && W && N > 0 && N % 2 == 0 && pf > 0 && a > 0 && alpha > 0 && method >= 0 &&
+                      method <= 2,
+                  "thx_reconstruct_weights: bad arguments");
+    THX_CHECK_ARG(!map || (fsc && nFsc > 0), "thx_reconstruct_weights: MAP needs the FSC");
+    const int vdim = N * pf;
+    const int maxR = maxRadius > 0 ? maxRadius : N / 2 - (int)std::ceil(a);
+    THX_CHECK_ARG(maxR > 0 && maxR <= N / 2, "thx_reconstruct_weights: bad maxRadius");
+    THX_CHECK_ARG(method != 2 || even_ok(vdim),
+                  "thx_reconstruct_weights: no even half-grid loop for vdim %d", vdim);
+    const size_t need = thx_reconstruct_workspace(N, pf);
+    THX_CHECK_ARG(need > 0 && workspace && wsBytes >= need,
+                  "thx_reconstruct_weights: workspace too small");
+    hipStream_t s = thx::as_stream(stream);
+    std::unique_lock<std::mutex> lk;
+    PlanEntry* pe = nullptr;
+    THX_RET(cached_plans(vdim, N, s, &pe, lk));
+    SolveBufs b;
+    THX_RET(solve_weights(pe, T, N, pf, a, alpha, gridCorr, maxR, map, fsc, nFsc, joinHalf, method,
+                          false, nIter, diffOut, workspace, wsBytes, s, b));
+    const size_t dimSize = (size_t)(vdim / 2 + 1) * vdim * vdim;
+    THX_HIP(hipMemcpyAsync(W, b.W, sizeof(float) * dimSize, hipMemcpyDeviceToDevice, s));
     THX_HIP(hipStreamSynchronize(s));
     return THX_OK;
 }

@@ -887,6 +887,30 @@ def reconstruct(hm, N, pf=2, a=1.9, alpha=15.0, grid_corr=True, max_radius=0, fs
     return dst, dft, n_it.value, [diffs[k] for k in range(n_it.value)]
 
 
+def reconstruct_weights(T, N, pf=2, a=1.9, alpha=15.0, grid_corr=True, max_radius=0, fsc=None,
+                        join_half=False, method=0):
+    """thx_reconstruct_weights: the balanced weights of thx_reconstruct's
+    solve for T [vdim, vdim, vdim/2+1] float32 (modified in place as the solve
+    does).  method 0: the solve's own balancing loop, 1: the 3D-transform
+    loop, 2: the even half-grid loop.  Returns (W, iterations, diffs)."""
+    vdim = pf * N
+    _req(T, torch.float32, (vdim, vdim, vdim // 2 + 1), "T")
+    dev = T.device
+    W = torch.empty_like(T)
+    n_it = ctypes.c_int(0)
+    diffs = (ctypes.c_float * 32)()
+    fs = None
+    if fsc is not None:
+        fs = torch.as_tensor(np.ascontiguousarray(fsc), dtype=torch.float64, device=dev)
+    ws = workspace(lib().thx_reconstruct_workspace(N, pf), dev)
+    check(lib().thx_reconstruct_weights(_ptr(T), N, pf, a, alpha, int(bool(grid_corr)), max_radius,
+                                        int(fs is not None), _ptr(fs),
+                                        0 if fs is None else fs.numel(), int(bool(join_half)),
+                                        int(method), _ptr(W), ctypes.byref(n_it), diffs, _ptr(ws),
+                                        ws.numel(), _stream(dev)), "thx_reconstruct_weights")
+    return W, n_it.value, [diffs[k] for k in range(n_it.value)]
+
+
 # ------------------------------------------------------------------ a14
 def fsc(A, B, n_shell):
     vdim = _vol_dim(A)
