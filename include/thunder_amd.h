@@ -1141,6 +1141,98 @@ int thx_subtract(const float* vol, int vdim, int pf, int nK, const float* oriFT,
                  double* quatOut, double* shift, void* workspace, size_t wsBytes,
                  thx_stream_t stream);
 
+/* ------------------------------------------------- mask generation ---
+ * genMask / removeIsolatedPoint / extMask / softEdge (src/Functions/Mask.cpp:
+ * 581-731) with thunder_genmask's corner removal (appsrc/thunder_genmask.cpp:
+ * 156-159), on device (csrc/mask.hip).  Real maps [N][N][N], origin at index
+ * 0, negatives wrapped; N even, 16 <= N <= 1024 (any such N: 48, 96, ...).
+ * autoMask's threshold search (:733-791) is not provided.
+ *
+ * thx_mask_threshold -- dst = src > thres ? 1 : 0 (:699-704), with
+ *   removeCorners a voxel with i^2 + j^2 + k^2 >= (N/2)^2 counting as 0 first,
+ *   then removeIsolatedPoint (:581-610): a 1-voxel none of whose six face
+ *   neighbours INSIDE THE BOX is 1 becomes 0, judged on the thresholded map,
+ *   not in place.  dst must not overlap src.
+ * thx_mask_extend -- extMask (:612-640).  ext > 0: dst = 1 wherever a voxel
+ *   equal to 1 lies at an integer offset d with |d|^2 < ext^2 (the reference's
+ *   comparison, a double against the RFLOAT square); ext < 0: dst = 0 wherever
+ *   a voxel equal to 0 inside the box lies that close; every other voxel keeps
+ *   src's value; ext = 0 copies.  The reference's grid loop runs [-a, a), a =
+ *   ceil|ext|, and -a never passes the strict test: the footprint is the open
+ *   ball.  dst may be src.
+ * thx_mask_soft_edge -- softEdge (:642-692).  d = the smallest |d| < ew (d the
+ *   RFLOAT value of sqrt of the integer |d|^2) to a voxel equal to 1; a voxel
+ *   with 0 < d < ew becomes 0.5 + 0.5 cos(d / ew pi) (FP32), every other voxel
+ *   keeps src's value; ew <= 0 copies.  dst may be src.
+ * thx_gen_mask -- the three chained on the stream (genMask, :721-731), the
+ *   last two in place on dst; dst must not overlap src.
+ * Box faces: nothing wraps and nothing is written outside the box.  The
+ *   reference indexes linearly with its bounds checks compiled out
+ *   (IMG_VOL_BOUNDARY_NO_CHECK): a footprint crossing a face is an out-of-row
+ *   write there, which is not reproduced.
+ * Limits: |ext| <= 32 and ew <= 32.  These and every other bad argument are
+ *   rejected before any device work.
+ * The binary map is packed to bits along x and every output voxel finds the
+ *   nearest set bit of each row (dy, dz) of the ball with count-leading /
+ *   -trailing zeros: about pi ew^2 row lookups, not (2a+1)^3 taps, and exact
+ *   (integer |d|^2).  No atomics, no host synchronisation, bit-identical from
+ *   run to run.
+ * thx_gen_mask_workspace (host) -- bytes for thx_mask_extend,
+ *   thx_mask_soft_edge and thx_gen_mask (the packed bits, N^2 ceil(N/64)
+ *   words); 0 for a bad N. */
+size_t thx_gen_mask_workspace(int N);
+int thx_mask_threshold(const float* src, int N, float thres, int removeCorners, float* dst,
+                       thx_stream_t stream);
+int thx_mask_extend(const float* src, int N, float ext, float* dst, void* workspace,
+                    size_t wsBytes, thx_stream_t stream);
+int thx_mask_soft_edge(const float* src, int N, float ew, float* dst, void* workspace,
+                       size_t wsBytes, thx_stream_t stream);
+int thx_gen_mask(const float* src, int N, float thres, float ext, float ew, int removeCorners,
+                 float* dst, void* workspace, size_t wsBytes, thx_stream_t stream);
+
+/* ----------------------------------------- masked / core-region FSC ---
+ * The maskFSC / coreFSC branch of Model::compareTwoHemispheres
+ * (src/Model.cpp:411-567), on device (csrc/fsc_masked.hip).  3D only: the
+ * reference refuses both options in 2D (:570-577).
+ *
+ * thx_fsc_masked -- A, B: half-complex [N][N][N/2+1], read-only and left
+ *   untouched.  Exactly one of alphaMask (real [N^3], origin at index 0: the
+ *   _maskFSC branch) and coreR > 0 (the _coreFSC branch: softMask(mask, coreR,
+ *   edge), src/Functions/Mask.cpp:466-487, evaluated in the multiply kernel,
+ *   never materialised; the reference's edge is EDGE_WIDTH_RL = 6) is given;
+ *   both or neither is an error.  N even, 16 <= N <= 1024; 2 <= nShell <= N/2.
+ *   method: as thx_fft3d's.  Stream-ordered steps, no host round trip:
+ *     1. fscUnmask = FSC(A, B) (src/Functions/Spectrum.cpp:302-337);
+ *     2. t = resP(fscUnmask, 0.8, 1, 1, false) (:339-363, the trailing result--
+ *        included; the threshold is the RFLOAT 0.8);
+ *     3. randomPhase (:365-386): stored voxel q (the flat half-complex index)
+ *        whose shell rint|(i, j, k)| > t is multiplied by exp(2 pi i u), u =
+ *        draw 0 of the Philox stream (q >> 32, q & 0xffffffff, tag), tag
+ *        0x72706841 for A and 0x72706842 for B, keyed by seed (the reference
+ *        draws from an urandom-seeded GSL generator), into a workspace copy;
+ *     4. bw (1 / N^3), x (1 - (1 - alpha)) (softMask with bg = 0,
+ *        Mask.cpp:533-544), fw, for the randomised copies -> fscRF and for
+ *        plain copies of A and B -> fscMask.  Before each bw the planes i = 0
+ *        and i = N/2 of the copy are replaced by their Hermitian part
+ *        (z(j, k) + conj z(-j, -k)) / 2: all FFTW's c2r reads of them, so the
+ *        result does not depend on how hipFFT or the column passes read an
+ *        inconsistent plane;
+ *     5. fsc[u] = fscMask[u] for u < t + 2, else (fscMask[u] - fscRF[u]) /
+ *        (1 - fscRF[u]); as in the reference there is NO guard on that divisor.
+ *   Outputs (device): fsc [nShell] FP64; curves (may be NULL) [3][nShell] FP64:
+ *   unmasked, masked, randomised-masked; thres (may be NULL): t as an int.
+ *   The shell sums of this entry are FP64 in a fixed order (per-block partials
+ *   and an ordered final pass, no atomics): the whole call is bit-identical
+ *   from run to run.  Bad arguments are rejected before any device work.
+ * thx_fsc_masked_workspace (host) -- bytes for thx_fsc_masked (two
+ *   half-complex copies, one real map, hipFFT's work area, the partial sums);
+ *   0 for bad arguments. */
+size_t thx_fsc_masked_workspace(int N, int nShell);
+int thx_fsc_masked(const float* A, const float* B, int N, int nShell, const float* alphaMask,
+                   float coreR, float edge, unsigned long long seed, int method, double* fsc,
+                   double* curves, int* thres, void* workspace, size_t wsBytes,
+                   thx_stream_t stream);
+
 /* HIP event pairs for thx_expect_cfg.phaseEvents: create n (begin, end)
  * pairs, read back ms[i] per pair (-1: not recorded), destroy. */
 int thx_event_pairs_create(int n, void** events);
