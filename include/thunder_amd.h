@@ -1233,6 +1233,89 @@ int thx_fsc_masked(const float* A, const float* B, int N, int nShell, const floa
                    double* curves, int* thres, void* workspace, size_t wsBytes,
                    thx_stream_t stream);
 
+/* ------------------------------------------------------ post-processing ---
+ * What Postprocess::run (src/Postprocess.cpp:50-183) does with the two final
+ * half-maps after its "true FSC" (thx_fsc_masked), on device
+ * (csrc/postprocess.hip); the same filters are thunder_lowpass
+ * (appsrc/thunder_lowpass.cpp:146-150) and thunder_bfactor.  Maps: half-complex
+ * [N][N][N/2+1] float2, unnormalised; real [N^3], origin at index 0, negatives
+ * wrapped; N even, 16 <= N <= 1024.  Every entry is stream-ordered, allocates
+ * nothing, reads nothing back, uses no atomics (bit-identical from run to
+ * run) and rejects bad arguments before any device work.  The shell index is
+ * rint(sqrt(i^2 + j^2 + k^2)) from the integer sum, as thx_fsc_masked's; the
+ * reference's FP32 expression AROUND(NORM_3(i/N, j/N, k/N) N) gives the same
+ * index at every stored voxel for N = 48, 96, 100, 200, 250, 384, 400, 500
+ * (counted in numpy: zero differences).
+ *
+ * thx_ft_merge_weight -- dst = (A + B) / 2 (mergeAB, Postprocess.cpp:207-213);
+ *   B NULL: dst = A.  fsc != NULL (device FP64 [nShell], 2 <= nShell <= N/2):
+ *   then times sqrt(max(0, 2 fsc[u] / (1 + fsc[u]))) for shell u < nShell and
+ *   exactly 0 beyond (fscWeightingFilter, src/Functions/Filter.cpp:144-167);
+ *   the weight is rounded to FP32 before the multiply (the reference's RFLOAT).
+ *   dst may be A.
+ * thx_bfactor_est -- bFactorEst (src/Functions/Spectrum.cpp:414-453): the sums
+ *   of |F| and the counts over the stored voxels with rL <= u < rU (the i = 0
+ *   plane once per stored voxel, as VOLUME_FOR_EACH_PIXEL_FT visits it), per
+ *   shell y = log(w[u] sum / count) and x = ((float)u / N)^2, the unweighted
+ *   least-squares slope c1 of y on x, bFactor = 2 c1.  1 <= rU <= N/2, rL >= 0.
+ *   rUdev != NULL (device int): the upper shell is min(*rUdev, rU) and rU is
+ *   the capacity of w and guinier, so a chain needs no read-back.  w (may be
+ *   NULL: 1): device FP64 [rU], a per-shell factor of |F| (constant on a
+ *   shell, so sum |w F| = w sum |F|).  The sums are FP64 in a fixed order and
+ *   the fit is FP64 (the reference accumulates in RFLOAT).  out: device
+ *   double[4] {bFactor, c0, nFit, status}; status 1 and bFactor 0 when
+ *   rU - rL < 2, a fit shell is empty, or a fit shell's sum is not positive
+ *   (the reference reads an undefined fit there).  guinier (may be NULL):
+ *   device [2][rU], x then y of fit point e = u - rL, 0 beyond nFit.
+ * thx_bfactor_est_workspace (host) -- its bytes; 0 for bad arguments.
+ * thx_ft_sharpen -- sharpen (Spectrum.cpp:402-412): bFactorFilter
+ *   (Filter.cpp:29-44: times exp(-0.5 b f^2), f^2 = (i/N)^2 + (j/N)^2 + (k/N)^2
+ *   in FP32), then lowPassFilter (:69-92) with f the FP32 norm, thres and ew
+ *   in 1 / box: f < thres keeps, f > thres + ew zeroes, otherwise times
+ *   cos((f - thres) pi / ew) / 2 + 0.5.  bFactorDev != NULL (device double):
+ *   b = bFactorDev[0]; thresDev != NULL (device int, a shell): thres =
+ *   (float)*thresDev / N.  ew <= 0 or thres < 0: no low pass; b == 0: no
+ *   B-factor factor.  dst may be src.
+ * thx_postprocess -- the chain.  The caller passes nShell = N/2 - 1 for the
+ *   reference's maxR().
+ *     1. thx_fsc_masked(A, B, N, nShell, alphaMask, 0, 0, seed, method) -> fsc,
+ *        curves (may be NULL), info[0] = t;
+ *     2. res = resP(fsc, 0.143, 1, 1, false) -> info[1] (RFLOAT threshold,
+ *        trailing result--);
+ *     3. rL = rint(N pixelSize / lowResA) in FP32 (host) -> info[2]
+ *        (B_FACTOR_EST_LOW_RES = 10);
+ *     4. pass 1 over A and B: thx_bfactor_est's sums of |A + B| / 2 over
+ *        [rL, res) with w = the FSC weight -> fit, guinier (may be NULL,
+ *        [2][nShell]), info[3] = nFit.  A finite bFactorIn skips this and is
+ *        used instead (fit = {bFactorIn, 0, 0, 0}); NaN: estimate;
+ *     5. pass 2 over A and B writes (A + B) / 2 times the FSC weight, times
+ *        exp(-0.5 b f^2), times the low pass with thres = res / N, ew =
+ *        edgeFT / N (EDGE_WIDTH_FT = 4), each product rounded to FP32;
+ *     6. planes i = 0 and i = N/2 <- their Hermitian part (as thx_fsc_masked),
+ *        inverse transform (method as thx_fft3d's), x 1/N^3, x (1 - (1 - alpha))
+ *        -> sharp [N^3];
+ *     7. average != NULL: the inverse transform of the plain merge x 1/N^3
+ *        (Reference_Average.mrc).
+ *   A and B are read-only and left untouched.  alphaMask, sharp and average
+ *   must be 16-byte aligned.
+ * thx_postprocess_workspace (host) -- its bytes (thx_fsc_masked's workspace,
+ *   reused after the FSC for the merged map and hipFFT's work area, plus the
+ *   partial sums); 0 for bad arguments. */
+int thx_ft_merge_weight(const float* A, const float* B, int N, const double* fsc, int nShell,
+                        float* dst, thx_stream_t stream);
+size_t thx_bfactor_est_workspace(int N, int rU);
+int thx_bfactor_est(const float* F, int N, int rL, int rU, const int* rUdev, const double* w,
+                    double* out, double* guinier, void* workspace, size_t wsBytes,
+                    thx_stream_t stream);
+int thx_ft_sharpen(const float* src, int N, float bFactor, const double* bFactorDev, float thres,
+                   const int* thresDev, float ew, float* dst, thx_stream_t stream);
+size_t thx_postprocess_workspace(int N, int nShell, int wantAverage);
+int thx_postprocess(const float* A, const float* B, int N, int nShell, const float* alphaMask,
+                    float pixelSize, float lowResA, float edgeFT, double bFactorIn,
+                    unsigned long long seed, int method, double* fsc, double* curves, int* info,
+                    double* fit, double* guinier, float* average, float* sharp, void* workspace,
+                    size_t wsBytes, thx_stream_t stream);
+
 /* HIP event pairs for thx_expect_cfg.phaseEvents: create n (begin, end)
  * pairs, read back ms[i] per pair (-1: not recorded), destroy. */
 int thx_event_pairs_create(int n, void** events);
