@@ -126,6 +126,15 @@ def test_curves_and_threshold_match_the_reference(N, method, noise):
         check(c, gpu_run(c, branch, method), f"{c.name} method={method} {branch}")
 
 
+def test_rows_longer_than_one_wave():
+    """N = 144: a row stores 73 voxels, so the shell sums take a second 64-lane chunk of every
+    row, and with nShell = 71 its lanes i = 64 .. 72 feed shells 64 .. 70 (at N = 128, nShell
+    63, the second chunk always starts past the last shell and contributes nothing)"""
+    c = real_case(144, 0.02)
+    assert c.N // 2 + 1 > 64 and c.n_shell > 64
+    check(c, gpu_run(c, "alpha", 1), f"{c.name} method=1 alpha")
+
+
 @pytest.mark.parametrize("N,method", SHAPES)
 def test_fourier_space_noise_on_every_stored_voxel(N, method):
     c = fourier_case(N)

@@ -142,9 +142,9 @@ def test_merge_weight_modes():
     assert np.array_equal(run(odd, B, fsc, torch.empty_like(A)), w)
 
 
-def test_bfactor_est_smallest_box():
-    """N = 16, rL = 1, rU = 7: host rU and rUdev, with and without w"""
-    N, rL, rU = 16, 1, 7
+def bfactor_est_case(N, rL, rU):
+    """the fit over [rL, rU) of a generated spectrum against ref.b_factor_est: host rU and
+    rUdev under a table of N / 2, with and without w; returns (F, u, run) to go on with"""
     rng = np.random.default_rng(8)
     u = ref.shell_index(N)
     F = (np.exp(2.0 - 30.0 * (u / N) ** 2) * (1 + 0.2 * rng.random(u.shape))
@@ -152,33 +152,44 @@ def test_bfactor_est_smallest_box():
     w = 0.5 + rng.random(N // 2)
     L = lib()
     ws = torch.empty(L.thx_bfactor_est_workspace(N, N // 2), dtype=torch.uint8, device=DEV)
-    Fd = T_(F)
 
-    def run(cap, r_dev, wd):
+    def run(Fd, cap, r_dev, wd):
         out = torch.full((4,), -7.0, dtype=torch.float64, device=DEV)
         g = torch.full((2, cap), -7.0, dtype=torch.float64, device=DEV)
         check(L.thx_bfactor_est(_ptr(Fd), N, rL, cap, _ptr(r_dev), _ptr(wd), _ptr(out), _ptr(g),
                                 _ptr(ws), ws.numel(), None))
         return out.cpu().numpy(), g.cpu().numpy()
+    Fd = T_(F)
     F64 = F.astype(np.complex128)
     for wd in (None, w):
-        Fw = F64 if wd is None else F64 * np.concatenate([w, np.zeros(8)])[np.minimum(u, N // 2)]
+        Fw = F64 if wd is None else F64 * np.concatenate([w, np.zeros(N // 2)])[np.minimum(u, N // 2)]
         b, c0, x, y, status = ref.b_factor_est(Fw, rU, rL)
         assert status == 0
         wt = None if wd is None else T_(w)
-        for out, g in (run(rU, None, wt),
-                       run(N // 2, torch.tensor([rU], dtype=torch.int32, device=DEV), wt)):
-            print(f"N=16 w={'yes' if wd is not None else 'no'}: bFactor {out[0]:.6f} ref {b:.6f}")
+        for out, g in (run(Fd, rU, None, wt),
+                       run(Fd, N // 2, torch.tensor([rU], dtype=torch.int32, device=DEV), wt)):
+            print(f"N={N} w={'yes' if wd is not None else 'no'}: bFactor {out[0]:.6f} ref {b:.6f}")
             assert out[2] == rU - rL and out[3] == 0
             assert abs(out[0] - b) <= 1e-5 * abs(b) and abs(out[1] - c0) <= 1e-5 * abs(b)
             assert np.abs(g[0, :rU - rL] - x).max() <= 1e-15
             assert np.abs(g[1, :rU - rL] - y).max() <= 1e-5 * abs(b)
             assert np.all(g[:, rU - rL:] == 0)
-    out, _ = run(2, None, None)                     # rU - rL = 1: no fit
+    return F, u, run
+
+
+def test_bfactor_est_smallest_box():
+    """N = 16, rL = 1, rU = 7: host rU and rUdev, with and without w"""
+    F, u, run = bfactor_est_case(16, 1, 7)
+    out, _ = run(T_(F), 2, None, None)              # rU - rL = 1: no fit
     assert out[0] == 0 and out[3] == 1
-    Fd = T_(np.where(u == 3, 0, F).astype(np.complex64))
-    out, _ = run(rU, None, None)                    # a fit shell's sum is not positive
-    assert out[0] == 0 and out[3] == 1
+    out, _ = run(T_(np.where(u == 3, 0, F).astype(np.complex64)), 7, None, None)
+    assert out[0] == 0 and out[3] == 1              # a fit shell's sum is not positive
+
+
+def test_bfactor_est_rows_longer_than_one_wave():
+    """N = 144, rL = 1, rU = 72: a row stores 73 voxels, so the sums take the second 64-lane
+    chunk of every row, whose lanes feed shells 64 .. 71"""
+    bfactor_est_case(144, 1, 72)
 
 
 @pytest.mark.parametrize("mode", ["b", "lowpass", "both"])

@@ -109,6 +109,23 @@ struct Carver {
 // (include/Image/Volume.h:567-575).
 THX_DEV int wrap_idx(int v, int n) { return v >= 0 ? v : v + n; }
 
+// the grid-stride loop of a 1D launch over n elements
+#define GRID_STRIDE(q, n) \
+    for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < (n); q += (long)gridDim.x * blockDim.x)
+
+// (i, j, k) of half-complex index q of a (dim/2+1) x dim x nz grid: i in [0, dim/2], j, k
+// wrapped to [-dim/2, dim/2)
+THX_DEV void hc_coord(long q, int dim, int& i, int& j, int& k)
+{
+    const int nc = dim / 2 + 1;
+    i = (int)(q % nc);
+    const long r = q / nc;
+    j = (int)(r % dim);
+    k = (int)(r / dim);
+    if (j >= dim / 2) j -= dim;
+    if (k >= dim / 2) k -= dim;
+}
+
 // a * b + c on the full-rate 24-bit multiplier (v_mad_u32_u24) for index
 // arithmetic whose factors are below 2^24 and whose result fits 32 bits.
 // Written out because the compiler folds __umul24 + add into the 64-bit

@@ -46,6 +46,9 @@ struct PlanEntry {
 // the entry for (current device, vdim, N, s), its plans made; returned locked
 int cached_plans(int vdim, int N, hipStream_t s, PlanEntry** out, std::unique_lock<std::mutex>& lock);
 
+// every plan of p that exists <- this work area (at least p.work bytes) and stream
+int bind_plans(const Plans& p, void* work, hipStream_t s);
+
 // The 3D C2R / R2C of box vdim with p's plans (method as thx_fft3d's); the
 // caller has bound their work area and stream.  C is overwritten either way.
 int c2r3d(const Plans& p, float2* C, float* rl, int vdim, hipStream_t s, int method = 0);

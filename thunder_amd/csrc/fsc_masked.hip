@@ -20,16 +20,14 @@
 // runs, reads of them; random phases leave them inconsistent, and how hipFFT or the column
 // passes read an inconsistent plane is their own choice (the precedent: subtract.hip).
 //
-// The shell sums are FP64 in a fixed order, without atomics: a wave takes whole rows (j, k)
-// with its lanes along i, where the shell index never decreases, so a segmented scan sums the
-// lanes of one shell and the segment's last lane adds the total to the wave's own LDS
-// histogram; the block adds its waves' histograms in wave order into its slot of the
-// workspace, and one block adds the slots in block order.  Everything is stream-ordered with no
-// host round trip, and the whole call is bit-identical from run to run.
+// The shell sums are FP64 in a fixed order, without atomics (volume.h: shell_pass per block,
+// sum_slots in the final block).  Everything is stream-ordered with no host round trip, and the
+// whole call is bit-identical from run to run.
 #include <cmath>
 
 #include "common.h"
 #include "fft_plans.h"
+#include "volume.h"
 
 namespace {
 
@@ -40,66 +38,20 @@ constexpr int FM_FINAL = 1024;          // threads of the final pass (3 nShell s
 constexpr uint32_t FM_TAG_A = 0x72706841u;   // "rphA": counter word c of A's phase stream
 constexpr uint32_t FM_TAG_B = 0x72706842u;   // "rphB"
 
-THX_DEV int signed_idx(int a, int n) { return a < n / 2 ? a : a - n; }
-
-// AROUND(NORM_3(i, j, k)) of an integer q2 = i^2 + j^2 + k^2 < 2^24: q2 is exact in FP32 and
-// sqrt(q2) is at least 0.25 / (2 sqrt(q2)) > 1e-4 away from any half-integer ((m + 1/2)^2 is
-// never an integer), far more than FP32's rounding at 887, so the FP32 root rounds to the
-// same integer as the FP64 one
-THX_DEV int shell_of(int q2) { return (int)rintf(sqrtf((float)q2)); }
-
 // part[block][3][nShell] = the block's sums of Re(a conj b), |a|^2, |b|^2 per shell
 __global__ void __launch_bounds__(FM_THREADS) k_shell_partial(const float2* __restrict__ A,
                                                               const float2* __restrict__ B, int N,
                                                               int nShell, double* __restrict__ part)
 {
     extern __shared__ double sh[];      // [FM_WAVES][3][nShell]
-    for (int s = threadIdx.x; s < FM_WAVES * 3 * nShell; s += FM_THREADS) sh[s] = 0.0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    double* mine = sh + (size_t)wv * 3 * nShell;
     const int nc = N / 2 + 1;
-    const long nRow = (long)N * N;
-    for (long row = (long)blockIdx.x * FM_WAVES + wv; row < nRow; row += (long)gridDim.x * FM_WAVES) {
-        const int j = signed_idx((int)(row % N), N), k = signed_idx((int)(row / N), N);
-        const int c2 = j * j + k * k;
-        for (int i0 = 0; i0 < nc; i0 += 64) {
-            // the shell grows with i: nothing further along this row is below nShell
-            if (shell_of(i0 * i0 + c2) >= nShell) break;
-            const int i = i0 + lane;
-            const int u = i < nc ? shell_of(i * i + c2) : 1 << 30;
-            double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-            if (u < nShell) {
-                const float2 a = A[row * nc + i], b = B[row * nc + i];
-                s0 = (double)a.x * b.x + (double)a.y * b.y;
-                s1 = (double)a.x * a.x + (double)a.y * a.y;
-                s2 = (double)b.x * b.x + (double)b.y * b.y;
-            }
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int uu = __shfl_up(u, o, 64);
-                const double t0 = __shfl_up(s0, o, 64), t1 = __shfl_up(s1, o, 64),
-                             t2 = __shfl_up(s2, o, 64);
-                if (lane >= o && uu == u) {
-                    s0 += t0;
-                    s1 += t1;
-                    s2 += t2;
-                }
-            }
-            const int un = __shfl_down(u, 1, 64);
-            if ((lane == 63 || un != u) && u < nShell) {
-                mine[u] += s0;
-                mine[nShell + u] += s1;
-                mine[2 * nShell + u] += s2;
-            }
-        }
-    }
-    __syncthreads();
-    for (int s = threadIdx.x; s < 3 * nShell; s += FM_THREADS) {
-        double t = 0.0;
-        for (int w = 0; w < FM_WAVES; w++) t += sh[(size_t)w * 3 * nShell + s];
-        part[(size_t)blockIdx.x * 3 * nShell + s] = t;
-    }
+    shell_pass<3, FM_WAVES>(sh, N, nShell, nShell, part, [=](long row, int i, int, double* s) {
+        const float2 a = A[row * nc + i], b = B[row * nc + i];
+        s[0] = (double)a.x * b.x + (double)a.y * b.y;
+        s[1] = (double)a.x * a.x + (double)a.y * a.y;
+        s[2] = (double)b.x * b.x + (double)b.y * b.y;
+        return true;
+    });
 }
 
 // one block: the slots in block order, the curve, and (thres != NULL) resP
@@ -110,19 +62,8 @@ __global__ void __launch_bounds__(FM_FINAL) k_shell_final(const double* __restri
 {
     extern __shared__ double acc[];     // [3][nShell], then the curve [nShell]
     double* cur = acc + 3 * nShell;
-    for (int s = threadIdx.x; s < 3 * nShell; s += FM_FINAL) {
-        double t = 0.0;
-        int b = 0;
-        for (; b + 16 <= nBlock; b += 16) {     // sixteen loads in flight, added in block order
-            double v[16];
-#pragma unroll
-            for (int e = 0; e < 16; e++) v[e] = part[(size_t)(b + e) * 3 * nShell + s];
-#pragma unroll
-            for (int e = 0; e < 16; e++) t += v[e];
-        }
-        for (; b < nBlock; b++) t += part[(size_t)b * 3 * nShell + s];
-        acc[s] = t;
-    }
+    for (int s = threadIdx.x; s < 3 * nShell; s += FM_FINAL)
+        acc[s] = sum_slots<3>(part, nBlock, nShell, s);
     __syncthreads();
     for (int u = threadIdx.x; u < nShell; u += FM_FINAL) {
         const double ab = sqrt(acc[nShell + u] * acc[2 * nShell + u]);
@@ -130,13 +71,7 @@ __global__ void __launch_bounds__(FM_FINAL) k_shell_final(const double* __restri
         curve[u] = cur[u];
     }
     __syncthreads();
-    if (thres && threadIdx.x == 0) {
-        const double thr = (double)0.8f;
-        int r = 1;
-        for (; r < nShell; r++)
-            if (cur[r] < thr) break;
-        *thres = r - 1;
-    }
+    if (thres && threadIdx.x == 0) *thres = res_p(cur, nShell, 0.8f);
 }
 
 __global__ void __launch_bounds__(FM_THREADS) k_random_phase(const float2* __restrict__ src,
@@ -221,17 +156,8 @@ __global__ void k_fsc_combine(const double* __restrict__ cur, const int* __restr
     if (thresOut && u == 0) *thresOut = t;
 }
 
-bool box_ok(int N) { return N >= 16 && N <= 1024 && N % 2 == 0; }
-bool shells_ok(int N, int nShell) { return nShell >= 2 && nShell <= N / 2; }
-size_t ft_elems(int N) { return (size_t)(N / 2 + 1) * N * N; }
-// room for hipFFT's work area, checked against the plans' at the call (as refresh.hip)
-size_t fft_reserve(int N) { return 2 * ft_elems(N) * sizeof(float2); }
-
-int shell_blocks(int N)
-{
-    const long b = ((long)N * N + FM_WAVES * 8 - 1) / (FM_WAVES * 8);
-    return (int)(b > FM_MAX_BLOCKS ? FM_MAX_BLOCKS : b);
-}
+int shell_blocks(int N) { return thx::shell_blocks(N, FM_WAVES, FM_MAX_BLOCKS); }
+unsigned stream_blocks(size_t n) { return thx::stream_blocks(n, FM_THREADS, 4096); }
 
 struct Carved {
     double* part = nullptr;
@@ -251,10 +177,10 @@ Carved carve(void* ws, size_t cap, int N, int nShell)
     c.part = k.take<double>((size_t)shell_blocks(N) * 3 * nShell);
     c.cur = k.take<double>((size_t)3 * nShell);
     c.thres = k.take<int>(1);
-    c.CA = k.take<float2>(ft_elems(N));
-    c.CB = k.take<float2>(ft_elems(N));
+    c.CA = k.take<float2>(thx::ft_elems(N));
+    c.CB = k.take<float2>(thx::ft_elems(N));
     c.rl = k.take<float>((size_t)N * N * N);
-    c.work = k.take<char>(fft_reserve(N));
+    c.work = k.take<char>(thx::fft_reserve(N));
     c.bytes = k.off + 256;
     return c;
 }
@@ -270,17 +196,18 @@ int shell_curve(const float2* A, const float2* B, int N, int nShell, double* par
     return THX_OK;
 }
 
-unsigned stream_blocks(size_t n)
-{
-    const size_t b = (n + FM_THREADS - 1) / FM_THREADS;
-    return (unsigned)(b > 4096 ? 4096 : b);
-}
-
 }  // namespace
+
+int thx::hermitian_planes(float2* ft, int N, hipStream_t s)
+{
+    THX_LAUNCH(k_hermitian_planes, dim3(thx::cdiv((long)2 * N * N, FM_THREADS)), dim3(FM_THREADS), 0,
+               s, ft, N);
+    return THX_OK;
+}
 
 extern "C" size_t thx_fsc_masked_workspace(int N, int nShell)
 {
-    if (!box_ok(N) || !shells_ok(N, nShell)) return 0;
+    if (!thx::box_ok(N) || !thx::shells_ok(N, nShell)) return 0;
     return carve(nullptr, ~size_t(0), N, nShell).bytes;
 }
 
@@ -289,8 +216,8 @@ extern "C" int thx_fsc_masked(const float* A, const float* B, int N, int nShell,
                               unsigned long long seed, int method, double* fsc, double* curves,
                               int* thres, void* workspace, size_t wsBytes, thx_stream_t stream)
 {
-    THX_CHECK_ARG(box_ok(N), "thx_fsc_masked: N=%d must be even, in [16, 1024]", N);
-    THX_CHECK_ARG(shells_ok(N, nShell), "thx_fsc_masked: nShell=%d outside [2, N/2]", nShell);
+    THX_CHECK_ARG(thx::box_ok(N), "thx_fsc_masked: N=%d must be even, in [16, 1024]", N);
+    THX_CHECK_ARG(thx::shells_ok(N, nShell), "thx_fsc_masked: nShell=%d outside [2, N/2]", nShell);
     THX_CHECK_ARG(method >= 0 && method <= 2, "thx_fsc_masked: method is 0, 1 or 2");
     THX_CHECK_ARG(method != 2 || (N & (N - 1)) == 0,
                   "thx_fsc_masked: the column passes need a power-of-two N");
@@ -310,15 +237,11 @@ extern "C" int thx_fsc_masked(const float* A, const float* B, int N, int nShell,
     THX_RET(thx::cached_plans(N, N / 2, s, &pe, lk));
     const thx::Plans& pl = pe->p;
     THX_CHECK_ARG(method != 2 || pl.cols, "thx_fsc_masked: no column passes for N=%d", N);
-    THX_CHECK_ARG(pl.work <= fft_reserve(N), "thx_fsc_masked: hipFFT's work area exceeds the reserve");
-    for (hipfftHandle h : {pl.c2r, pl.r2c, pl.c2rX, pl.r2cX}) {
-        if (!h) continue;
-        THX_FFT(hipfftSetWorkArea(h, c.work));
-        THX_FFT(hipfftSetStream(h, s));
-    }
+    THX_CHECK_ARG(pl.work <= thx::fft_reserve(N), "thx_fsc_masked: hipFFT's work area exceeds the reserve");
+    THX_RET(thx::bind_plans(pl, c.work, s));
     const float2* A2 = reinterpret_cast<const float2*>(A);
     const float2* B2 = reinterpret_cast<const float2*>(B);
-    const size_t nFT = ft_elems(N), n3 = (size_t)N * N * N;
+    const size_t nFT = thx::ft_elems(N), n3 = (size_t)N * N * N;
     const float scale = 1.f / ((float)N * (float)N * (float)N);
     THX_RET(shell_curve(A2, B2, N, nShell, c.part, c.cur, c.thres, s));
     for (int pass = 0; pass < 2; pass++) {      // 0: randomised -> cur[2], 1: plain -> cur[1]
@@ -332,8 +255,7 @@ extern "C" int thx_fsc_masked(const float* A, const float* B, int N, int nShell,
             THX_HIP(hipMemcpyAsync(c.CB, B, nFT * sizeof(float2), hipMemcpyDeviceToDevice, s));
         }
         for (float2* C : {c.CA, c.CB}) {
-            THX_LAUNCH(k_hermitian_planes, dim3(thx::cdiv((long)2 * N * N, FM_THREADS)),
-                       dim3(FM_THREADS), 0, s, C, N);
+            THX_RET(thx::hermitian_planes(C, N, s));
             THX_RET(thx::c2r3d(pl, C, c.rl, N, s, method));
             THX_LAUNCH(k_mask_mul, dim3(stream_blocks(n3)), dim3(FM_THREADS), 0, s, c.rl, alphaMask,
                        N, coreR, edge, scale);

@@ -45,6 +45,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "volume.h"
 
 namespace {
 
@@ -56,7 +57,6 @@ constexpr int MK_FAR = 1 << 30;
 
 enum { MK_EXTEND = 0, MK_ERODE = 1, MK_SOFT = 2 };
 
-bool box_ok(int N) { return N >= 16 && N <= 1024 && N % 2 == 0; }
 int row_words(int N) { return (N + 63) / 64; }
 size_t bits_bytes(int N) { return (size_t)N * N * row_words(N) * sizeof(uint64_t); }
 
@@ -280,14 +280,14 @@ int soft_impl(const float* src, int N, float ew, float* dst, uint64_t* bits, hip
 
 extern "C" size_t thx_gen_mask_workspace(int N)
 {
-    if (!box_ok(N)) return 0;
+    if (!thx::box_ok(N)) return 0;
     return bits_bytes(N) + 256;
 }
 
 extern "C" int thx_mask_threshold(const float* src, int N, float thres, int removeCorners,
                                   float* dst, thx_stream_t stream)
 {
-    THX_CHECK_ARG(box_ok(N), "thx_mask_threshold: N=%d must be even, in [16, 1024]", N);
+    THX_CHECK_ARG(thx::box_ok(N), "thx_mask_threshold: N=%d must be even, in [16, 1024]", N);
     THX_CHECK_ARG(src && dst, "thx_mask_threshold: src / dst is NULL");
     THX_CHECK_ARG(!aliases(src, dst, N), "thx_mask_threshold: dst aliases src");
     THX_CHECK_ARG(std::isfinite(thres), "thx_mask_threshold: thres is not finite");
@@ -297,7 +297,7 @@ extern "C" int thx_mask_threshold(const float* src, int N, float thres, int remo
 }
 
 #define MK_CHECK_COMMON(name)                                                                    \
-    THX_CHECK_ARG(box_ok(N), name ": N=%d must be even, in [16, 1024]", N);                      \
+    THX_CHECK_ARG(thx::box_ok(N), name ": N=%d must be even, in [16, 1024]", N);                      \
     THX_CHECK_ARG(src && dst, name ": src / dst is NULL");                                       \
     THX_CHECK_ARG(src == dst || !aliases(src, dst, N), name ": dst overlaps src without being it"); \
     THX_CHECK_ARG(workspace && wsBytes >= thx_gen_mask_workspace(N),                             \
@@ -332,7 +332,7 @@ extern "C" int thx_gen_mask(const float* src, int N, float thres, float ext, flo
     THX_CHECK_ARG(std::fabs(ext) <= (float)MK_LIMIT, "thx_gen_mask: |ext|=%g above %d",
                   (double)std::fabs(ext), MK_LIMIT);
     THX_CHECK_ARG(ew <= (float)MK_LIMIT, "thx_gen_mask: ew=%g above %d", (double)ew, MK_LIMIT);
-    THX_CHECK_ARG(box_ok(N), "thx_gen_mask: N=%d must be even, in [16, 1024]", N);
+    THX_CHECK_ARG(thx::box_ok(N), "thx_gen_mask: N=%d must be even, in [16, 1024]", N);
     THX_CHECK_ARG(src && dst, "thx_gen_mask: src / dst is NULL");
     THX_CHECK_ARG(!aliases(src, dst, N), "thx_gen_mask: dst aliases src");
     THX_CHECK_ARG(std::isfinite(thres), "thx_gen_mask: thres is not finite");

@@ -12,23 +12,21 @@
 //   pass 2  k_ft_stream: (A + B) / 2, times the FSC weight, times exp(-0.5 b f^2), times the low
 //           pass, each product rounded to FP32 as the reference's three sweeps round
 //
-// The shell index is rint(sqrt(i^2 + j^2 + k^2)) from the integer q2, as in fsc_masked.hip.
+// The shell index is rint(sqrt(i^2 + j^2 + k^2)) from the integer q2 (volume.h's shell_of).
 // fscWeightingFilter's literal FP32 expression AROUND(NORM_3(i/N, j/N, k/N) N) gives the same
 // index at every stored voxel for N = 48, 96, 100, 200, 250, 384, 400 and 500 (counted in
 // numpy: zero differences; tests/postprocess_ref.py holds both forms and
 // tests/test_postprocess.py compares them at N = 32, 48 and 100).
 //
-// The Guinier sums are FP64 in a fixed order without atomics, the scheme of fsc_masked.hip's
-// k_shell_partial / k_shell_final restated for one sum and one count: a wave takes whole rows
-// with its lanes along i, where the shell never decreases, a segmented scan sums the lanes of
-// one shell, the segment's last lane adds to the wave's LDS histogram, the block adds its
-// waves in wave order into its workspace slot, one block adds the slots in block order.  The
-// fit itself runs in FP64 in that last block (the reference accumulates in RFLOAT).
+// The Guinier sums (one sum and one count per shell) are FP64 in a fixed order without atomics
+// (volume.h: shell_pass per block, sum_slots in the final block).  The fit itself runs in FP64
+// in that last block (the reference accumulates in RFLOAT).
 // Everything is stream-ordered, nothing is allocated, nothing is read back.
 #include <cmath>
 
 #include "common.h"
 #include "fft_plans.h"
+#include "volume.h"
 
 namespace {
 
@@ -39,11 +37,6 @@ constexpr int PP_FINAL = 1024;
 constexpr unsigned PP_STREAM_BLOCKS = 2048;   // grid cap of the streaming kernels: eight
                                               // 256-thread blocks per CU (k_ft_stream holds five
                                               // at its 94 VGPRs, k_pp_scale_mask all eight)
-
-THX_DEV int signed_idx(int a, int n) { return a < n / 2 ? a : a - n; }
-
-// AROUND(NORM_3(i, j, k)) of an integer q2 < 2^24: see fsc_masked.hip's shell_of
-THX_DEV int shell_of(int q2) { return (int)rintf(sqrtf((float)q2)); }
 
 // sqrt(max(0, 2 fsc / (1 + fsc))) as the reference's RFLOAT
 THX_DEV float fsc_weight(double f) { return (float)sqrt(fmax(0.0, 2.0 * f / (1.0 + f))); }
@@ -146,6 +139,9 @@ __global__ void __launch_bounds__(PP_THREADS) k_ft_stream(const StreamArgs a)
     }
 }
 
+// the fit's upper shell: nTab, or *rUdev clamped to [0, nTab]
+THX_DEV int upper_shell(const int* rUdev, int nTab) { return rUdev ? min(max(*rUdev, 0), nTab) : nTab; }
+
 // part[block][2][nTab] = the block's sums of |F| and of 1 over the stored voxels of shells
 // [rL, rU); F = A, or (A + B) / 2 rounded to FP32 as mergeAB stores it
 __global__ void __launch_bounds__(PP_THREADS) k_guinier_partial(const float2* __restrict__ A,
@@ -155,55 +151,19 @@ __global__ void __launch_bounds__(PP_THREADS) k_guinier_partial(const float2* __
                                                                 double* __restrict__ part)
 {
     extern __shared__ double sh[];      // [PP_WAVES][2][nTab]
-    for (int s = threadIdx.x; s < PP_WAVES * 2 * nTab; s += PP_THREADS) sh[s] = 0.0;
-    __syncthreads();
-    int rU = nTab;
-    if (rUdev) rU = min(max(*rUdev, 0), nTab);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    double* mine = sh + (size_t)wv * 2 * nTab;
     const int nc = N / 2 + 1;
-    const long nRow = (long)N * N;
-    for (long row = (long)blockIdx.x * PP_WAVES + wv; row < nRow; row += (long)gridDim.x * PP_WAVES) {
-        const int j = signed_idx((int)(row % N), N), k = signed_idx((int)(row / N), N);
-        const int c2 = j * j + k * k;
-        for (int i0 = 0; i0 < nc; i0 += 64) {
-            // the shell grows with i: nothing further along this row is below rU
-            if (shell_of(i0 * i0 + c2) >= rU) break;
-            const int i = i0 + lane;
-            const int u = i < nc ? shell_of(i * i + c2) : 1 << 30;
-            const bool in = u < rU && u >= rL;
-            double s0 = 0.0, s1 = 0.0;
-            if (in) {
-                float2 v = A[row * nc + i];
-                if (B) {
-                    const float2 vb = B[row * nc + i];
-                    v = make_float2((v.x + vb.x) / 2, (v.y + vb.y) / 2);
-                }
-                s0 = sqrt((double)v.x * v.x + (double)v.y * v.y);
-                s1 = 1.0;
-            }
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int uu = __shfl_up(u, o, 64);
-                const double t0 = __shfl_up(s0, o, 64), t1 = __shfl_up(s1, o, 64);
-                if (lane >= o && uu == u) {
-                    s0 += t0;
-                    s1 += t1;
-                }
-            }
-            const int un = __shfl_down(u, 1, 64);
-            if ((lane == 63 || un != u) && in) {
-                mine[u] += s0;
-                mine[nTab + u] += s1;
-            }
+    shell_pass<2, PP_WAVES>(sh, N, nTab, upper_shell(rUdev, nTab), part,
+                            [=](long row, int i, int u, double* s) {
+        if (u < rL) return false;
+        float2 v = A[row * nc + i];
+        if (B) {
+            const float2 vb = B[row * nc + i];
+            v = make_float2((v.x + vb.x) / 2, (v.y + vb.y) / 2);
         }
-    }
-    __syncthreads();
-    for (int s = threadIdx.x; s < 2 * nTab; s += PP_THREADS) {
-        double t = 0.0;
-        for (int w = 0; w < PP_WAVES; w++) t += sh[(size_t)w * 2 * nTab + s];
-        part[(size_t)blockIdx.x * 2 * nTab + s] = t;
-    }
+        s[0] = sqrt((double)v.x * v.x + (double)v.y * v.y);
+        s[1] = 1.0;
+        return true;
+    });
 }
 
 // one block: the slots in block order, then the fit.  GSL's unweighted fit_linear:
@@ -217,23 +177,10 @@ __global__ void __launch_bounds__(PP_FINAL) k_guinier_fit(const double* __restri
                                                           int* __restrict__ nFitOut)
 {
     extern __shared__ double acc[];     // [2][nTab] sums and counts, then x and y
-    for (int s = threadIdx.x; s < 2 * nTab; s += PP_FINAL) {
-        double t = 0.0;
-        int b = 0;
-        for (; b + 16 <= nBlock; b += 16) {
-            double v[16];
-#pragma unroll
-            for (int e = 0; e < 16; e++) v[e] = part[(size_t)(b + e) * 2 * nTab + s];
-#pragma unroll
-            for (int e = 0; e < 16; e++) t += v[e];
-        }
-        for (; b < nBlock; b++) t += part[(size_t)b * 2 * nTab + s];
-        acc[s] = t;
-    }
+    for (int s = threadIdx.x; s < 2 * nTab; s += PP_FINAL)
+        acc[s] = sum_slots<2>(part, nBlock, nTab, s);
     __syncthreads();
-    int rU = nTab;
-    if (rUdev) rU = min(max(*rUdev, 0), nTab);
-    const int n = rU - rL;
+    const int rU = upper_shell(rUdev, nTab), n = rU - rL;
     __shared__ int bad;
     if (threadIdx.x == 0) bad = n < 2;
     __syncthreads();
@@ -277,9 +224,8 @@ __global__ void __launch_bounds__(PP_FINAL) k_guinier_fit(const double* __restri
     if (nFitOut) *nFitOut = n > 0 ? n : 0;
 }
 
-// the chain's small step between the FSC and pass 1: res = resP(fsc, 0.143, 1, 1, false) (the
-// RFLOAT threshold and the trailing result--, as k_shell_final's 0.8 search), the FSC weight
-// per shell as a double for the fit, and, with a given B-factor, the fit's outputs
+// the chain's small step between the FSC and pass 1: res = resP(fsc, 0.143, 1, 1, false), the
+// FSC weight per shell as a double for the fit, and, with a given B-factor, the fit's outputs
 __global__ void k_pp_prepare(const double* __restrict__ fsc, int nShell, int rL, double bIn,
                              int given, int* __restrict__ info, double* __restrict__ wd,
                              double* __restrict__ fit, double* __restrict__ guinier)
@@ -289,38 +235,13 @@ __global__ void k_pp_prepare(const double* __restrict__ fsc, int nShell, int rL,
         if (given && guinier) guinier[u] = guinier[nShell + u] = 0.0;
     }
     if (threadIdx.x != 0) return;
-    const double thr = (double)0.143f;
-    int r = 1;
-    for (; r < nShell; r++)
-        if (fsc[r] < thr) break;
-    info[1] = r - 1;
+    info[1] = res_p(fsc, nShell, 0.143f);
     info[2] = rL;
     if (given) {
         info[3] = 0;
         fit[0] = bIn;
         fit[1] = fit[2] = fit[3] = 0.0;
     }
-}
-
-// planes i = 0 and i = N/2 <- their Hermitian part: fsc_masked.hip's k_hermitian_planes
-// restated (all FFTW's c2r reads of them; how hipFFT or the column passes read an
-// inconsistent plane is their own choice)
-__global__ void __launch_bounds__(PP_THREADS) k_pp_hermitian_planes(float2* __restrict__ ft, int N)
-{
-    const int nc = N / 2 + 1;
-    const size_t tot = (size_t)2 * N * N;
-    const size_t e = blockIdx.x * (size_t)PP_THREADS + threadIdx.x;
-    if (e >= tot) return;
-    const int col = e < (size_t)N * N ? 0 : N / 2;
-    const size_t r = e % ((size_t)N * N);
-    const int jr = (int)(r % N), kr = (int)(r / N);
-    const size_t a = ((size_t)kr * N + jr) * nc + col;
-    const size_t b = ((size_t)((N - kr) % N) * N + (N - jr) % N) * nc + col;
-    if (a > b) return;
-    const float2 va = ft[a], vb = ft[b];
-    const float2 h = make_float2((va.x + vb.x) * 0.5f, (va.y - vb.y) * 0.5f);
-    ft[a] = h;
-    if (a != b) ft[b] = make_float2(h.x, -h.y);
 }
 
 // after the C2R, in place: bw's 1 / N^3, then softMask with bg = 0 (alpha NULL: the scale only)
@@ -343,30 +264,16 @@ __global__ void __launch_bounds__(PP_THREADS) k_pp_scale_mask(float* __restrict_
     }
 }
 
-bool box_ok(int N) { return N >= 16 && N <= 1024 && N % 2 == 0; }
-bool shells_ok(int N, int nShell) { return nShell >= 2 && nShell <= N / 2; }
-size_t ft_elems(int N) { return (size_t)(N / 2 + 1) * N * N; }
-size_t fft_reserve(int N) { return 2 * ft_elems(N) * sizeof(float2); }
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-int guinier_blocks(int N)
-{
-    const long b = ((long)N * N + PP_WAVES * 8 - 1) / (PP_WAVES * 8);
-    return (int)(b > PP_MAX_BLOCKS ? PP_MAX_BLOCKS : b);
-}
-
-unsigned stream_blocks(size_t n)
-{
-    const size_t b = (n + PP_THREADS - 1) / PP_THREADS;
-    return (unsigned)(b > PP_STREAM_BLOCKS ? PP_STREAM_BLOCKS : b);
-}
+int guinier_blocks(int N) { return thx::shell_blocks(N, PP_WAVES, PP_MAX_BLOCKS); }
+unsigned stream_blocks(size_t n) { return thx::stream_blocks(n, PP_THREADS, PP_STREAM_BLOCKS); }
 
 size_t guinier_bytes(int N, int nTab) { return (size_t)guinier_blocks(N) * 2 * nTab * sizeof(double) + 256; }
 
 int launch_stream(const StreamArgs& a, hipStream_t s)
 {
     const size_t lds = a.fsc ? sizeof(float) * a.nShell : 0;
-    const size_t n = ft_elems(a.N);
+    const size_t n = thx::ft_elems(a.N);
     if (aligned16(a.A) && aligned16(a.dst) && (!a.B || aligned16(a.B)))
         THX_LAUNCH(k_ft_stream<2>, dim3(stream_blocks(n / 2)), dim3(PP_THREADS), lds, s, a);
     else
@@ -401,7 +308,7 @@ Carved carve(void* ws, size_t cap, int N, int nShell)
     c.part = k.take<double>((size_t)guinier_blocks(N) * 2 * nShell);
     c.wd = k.take<double>(nShell);
     c.sharedBytes = thx_fsc_masked_workspace(N, nShell);
-    const size_t own = ft_elems(N) * sizeof(float2) + 256 + fft_reserve(N);
+    const size_t own = thx::ft_elems(N) * sizeof(float2) + 256 + thx::fft_reserve(N);
     if (c.sharedBytes < own) c.sharedBytes = own;
     c.shared = k.take<char>(c.sharedBytes);
     c.bytes = k.off + 256;
@@ -413,8 +320,8 @@ Carved carve(void* ws, size_t cap, int N, int nShell)
 extern "C" int thx_ft_merge_weight(const float* A, const float* B, int N, const double* fsc,
                                    int nShell, float* dst, thx_stream_t stream)
 {
-    THX_CHECK_ARG(box_ok(N), "thx_ft_merge_weight: N=%d must be even, in [16, 1024]", N);
-    THX_CHECK_ARG(!fsc || shells_ok(N, nShell), "thx_ft_merge_weight: nShell=%d outside [2, N/2]",
+    THX_CHECK_ARG(thx::box_ok(N), "thx_ft_merge_weight: N=%d must be even, in [16, 1024]", N);
+    THX_CHECK_ARG(!fsc || thx::shells_ok(N, nShell), "thx_ft_merge_weight: nShell=%d outside [2, N/2]",
                   nShell);
     THX_CHECK_ARG(A && dst, "thx_ft_merge_weight: A / dst is NULL");
     StreamArgs a{};
@@ -429,7 +336,7 @@ extern "C" int thx_ft_merge_weight(const float* A, const float* B, int N, const 
 
 extern "C" size_t thx_bfactor_est_workspace(int N, int rU)
 {
-    if (!box_ok(N) || rU < 1 || rU > N / 2) return 0;
+    if (!thx::box_ok(N) || rU < 1 || rU > N / 2) return 0;
     return guinier_bytes(N, rU);
 }
 
@@ -437,7 +344,7 @@ extern "C" int thx_bfactor_est(const float* F, int N, int rL, int rU, const int*
                                const double* w, double* out, double* guinier, void* workspace,
                                size_t wsBytes, thx_stream_t stream)
 {
-    THX_CHECK_ARG(box_ok(N), "thx_bfactor_est: N=%d must be even, in [16, 1024]", N);
+    THX_CHECK_ARG(thx::box_ok(N), "thx_bfactor_est: N=%d must be even, in [16, 1024]", N);
     THX_CHECK_ARG(rU >= 1 && rU <= N / 2, "thx_bfactor_est: rU=%d outside [1, N/2]", rU);
     THX_CHECK_ARG(rL >= 0, "thx_bfactor_est: rL=%d is negative", rL);
     THX_CHECK_ARG(F && out, "thx_bfactor_est: F / out is NULL");
@@ -454,7 +361,7 @@ extern "C" int thx_ft_sharpen(const float* src, int N, float bFactor, const doub
                               float thres, const int* thresDev, float ew, float* dst,
                               thx_stream_t stream)
 {
-    THX_CHECK_ARG(box_ok(N), "thx_ft_sharpen: N=%d must be even, in [16, 1024]", N);
+    THX_CHECK_ARG(thx::box_ok(N), "thx_ft_sharpen: N=%d must be even, in [16, 1024]", N);
     THX_CHECK_ARG(bFactorDev || std::isfinite(bFactor), "thx_ft_sharpen: bFactor is not finite");
     THX_CHECK_ARG(thresDev || std::isfinite(thres), "thx_ft_sharpen: thres is not finite");
     THX_CHECK_ARG(std::isfinite(ew), "thx_ft_sharpen: ew is not finite");
@@ -475,7 +382,7 @@ extern "C" int thx_ft_sharpen(const float* src, int N, float bFactor, const doub
 extern "C" size_t thx_postprocess_workspace(int N, int nShell, int wantAverage)
 {
     (void)wantAverage;          // the average reuses the sharpened map's half-complex buffer
-    if (!box_ok(N) || !shells_ok(N, nShell)) return 0;
+    if (!thx::box_ok(N) || !thx::shells_ok(N, nShell)) return 0;
     return carve(nullptr, ~size_t(0), N, nShell).bytes;
 }
 
@@ -486,8 +393,8 @@ extern "C" int thx_postprocess(const float* A, const float* B, int N, int nShell
                                float* average, float* sharp, void* workspace, size_t wsBytes,
                                thx_stream_t stream)
 {
-    THX_CHECK_ARG(box_ok(N), "thx_postprocess: N=%d must be even, in [16, 1024]", N);
-    THX_CHECK_ARG(shells_ok(N, nShell), "thx_postprocess: nShell=%d outside [2, N/2]", nShell);
+    THX_CHECK_ARG(thx::box_ok(N), "thx_postprocess: N=%d must be even, in [16, 1024]", N);
+    THX_CHECK_ARG(thx::shells_ok(N, nShell), "thx_postprocess: nShell=%d outside [2, N/2]", nShell);
     THX_CHECK_ARG(method >= 0 && method <= 2, "thx_postprocess: method is 0, 1 or 2");
     THX_CHECK_ARG(method != 2 || (N & (N - 1)) == 0,
                   "thx_postprocess: the column passes need a power-of-two N");
@@ -521,18 +428,14 @@ extern "C" int thx_postprocess(const float* A, const float* B, int N, int nShell
                                s));
     // the FSC is done with its workspace: the merged map and hipFFT's work area live there now
     float2* C = reinterpret_cast<float2*>(c.shared);
-    char* work = c.shared + ((ft_elems(N) * sizeof(float2) + 255) & ~size_t(255));
+    char* work = c.shared + ((thx::ft_elems(N) * sizeof(float2) + 255) & ~size_t(255));
     std::unique_lock<std::mutex> lk;
     thx::PlanEntry* pe = nullptr;
     THX_RET(thx::cached_plans(N, N / 2, s, &pe, lk));
     const thx::Plans& pl = pe->p;
     THX_CHECK_ARG(method != 2 || pl.cols, "thx_postprocess: no column passes for N=%d", N);
-    THX_CHECK_ARG(pl.work <= fft_reserve(N), "thx_postprocess: hipFFT's work area exceeds the reserve");
-    for (hipfftHandle h : {pl.c2r, pl.r2c, pl.c2rX, pl.r2cX}) {
-        if (!h) continue;
-        THX_FFT(hipfftSetWorkArea(h, work));
-        THX_FFT(hipfftSetStream(h, s));
-    }
+    THX_CHECK_ARG(pl.work <= thx::fft_reserve(N), "thx_postprocess: hipFFT's work area exceeds the reserve");
+    THX_RET(thx::bind_plans(pl, work, s));
     const size_t n3 = (size_t)N * N * N;
     const float scale = 1.f / ((float)N * (float)N * (float)N);
     for (int pass = 0; pass < (average ? 2 : 1); pass++) {      // 0: sharp, 1: the plain average
@@ -550,8 +453,7 @@ extern "C" int thx_postprocess(const float* A, const float* B, int N, int nShell
             a.lowPass = a.ew > 0.f;
         }
         THX_RET(launch_stream(a, s));
-        THX_LAUNCH(k_pp_hermitian_planes, dim3(thx::cdiv((long)2 * N * N, PP_THREADS)),
-                   dim3(PP_THREADS), 0, s, C, N);
+        THX_RET(thx::hermitian_planes(C, N, s));
         float* rl = pass == 0 ? sharp : average;
         THX_RET(thx::c2r3d(pl, C, rl, N, s, method));
         THX_LAUNCH(k_pp_scale_mask, dim3(stream_blocks(n3 / 4)), dim3(PP_THREADS), 0, s, rl,

@@ -31,24 +31,13 @@
 // One workgroup per image for the statistics (two passes, double sums);
 // hipFFT batched 2D transforms with plans cached per (device, N, batch,
 // stream).
-#include <hipfft/hipfft.h>
-
 #include <cmath>
 #include <map>
 #include <mutex>
 #include <tuple>
 
 #include "common.h"
-
-#define THX_FFT(call)                                                          \
-    do {                                                                       \
-        hipfftResult r_ = (call);                                              \
-        if (r_ != HIPFFT_SUCCESS) {                                            \
-            ::thx::set_error("%s:%d %s: hipfft error %d", __FILE__, __LINE__,  \
-                             #call, (int)r_);                                  \
-            return THX_ERR_HIP;                                                \
-        }                                                                      \
-    } while (0)
+#include "fft_plans.h"
 
 namespace {
 

@@ -32,23 +32,12 @@
 // Layouts: half-complex arrays [k][j][i] of (dim/2+1) x dim (x dim) with j, k
 // wrapped (Volume / Image FT = hipFFT R2C), real-space arrays [k][j][i] with
 // the origin at index 0 (Volume / Image RL).  2D calls are the nz = 1 case.
-#include <hipfft/hipfft.h>
-
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "adapter.h"
-
-#define THX_FFT(call)                                                          \
-    do {                                                                       \
-        hipfftResult r_ = (call);                                              \
-        if (r_ != HIPFFT_SUCCESS) {                                            \
-            ::thx::set_error("%s:%d %s: hipfft error %d", __FILE__, __LINE__, \
-                             #call, (int)r_);                                  \
-            return THX_ERR_HIP;                                                \
-        }                                                                      \
-    } while (0)
+#include "fft_plans.h"
 
 using thx::DBuf;
 using thx::DeviceGuard;
@@ -60,22 +49,7 @@ constexpr double PI_2_REF = 6.28318530717959;   // PI_2 (gpu/include/acc/Constru
 constexpr double DIFF_C_THRES = 1e-2, DIFF_C_DECREASE_THRES = 0.95;   // include/Reconstructor.h:65-69
 constexpr int N_DIFF_C_NO_DECREASE = 2;
 
-#define GRID_STRIDE(q, n) \
-    for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < (n); q += (long)gridDim.x * blockDim.x)
-
 inline unsigned grid_for(long n) { return (unsigned)std::min<long>(thx::cdiv(n, 256), 65536L); }
-
-// (i, j, k) of half-complex index q of a (dim/2+1) x dim x nz grid
-THX_DEV void hc_coord(long q, int dim, int& i, int& j, int& k)
-{
-    const int nc = dim / 2 + 1;
-    i = (int)(q % nc);
-    const long r = q / nc;
-    j = (int)(r % dim);
-    k = (int)(r / dim);
-    if (j >= dim / 2) j -= dim;
-    if (k >= dim / 2) k -= dim;
-}
 
 // |z| as kernel_RecalculateW / kernel_CheckCMAX compute it
 THX_DEV float mode_of(float2 c)

@@ -55,22 +55,6 @@ namespace {
 
 constexpr int TAB_N = 100000;   // _kernelRL.init(MKB_RL_R2, 0, 1, 1e5) (src/Reconstructor.cpp:77-88)
 
-
-// k of a half-complex index: i in [0, vdim/2], j, k wrapped to [-vdim/2, vdim/2)
-THX_DEV void ft_coord(long q, int vdim, int& i, int& j, int& k)
-{
-    const int nc = vdim / 2 + 1;
-    i = (int)(q % nc);
-    const long r = q / nc;
-    j = (int)(r % vdim);
-    k = (int)(r / vdim);
-    if (j >= vdim / 2) j -= vdim;
-    if (k >= vdim / 2) k -= vdim;
-}
-
-#define GRID_STRIDE(q, n) \
-    for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < (n); q += (long)gridDim.x * blockDim.x)
-
 __global__ void k_wiener(float* __restrict__ T, int vdim, int pf, int maxR,
                          const double* __restrict__ fsc, int nFsc, int joinHalf)
 {
@@ -79,7 +63,7 @@ __global__ void k_wiener(float* __restrict__ T, int vdim, int pf, int maxR,
     GRID_STRIDE(q, n)
     {
         int i, j, k;
-        ft_coord(q, vdim, i, j, k);
+        hc_coord(q, vdim, i, j, k);
         const long quad = (long)i * i + (long)j * j + (long)k * k;
         if (quad < lo || quad >= hi) continue;
         const int u = (int)rintf(sqrtf((float)quad));            // AROUND(NORM_3)
@@ -97,7 +81,7 @@ __global__ void k_init_w(float* __restrict__ W, float* __restrict__ T, int vdim,
     GRID_STRIDE(q, n)
     {
         int i, j, k;
-        ft_coord(q, vdim, i, j, k);
+        hc_coord(q, vdim, i, j, k);
         W[q] = ((long)i * i + (long)j * j + (long)k * k < r2) ? 1.f : 0.f;
         T[q] = fmaxf(T[q], 1e-25f);
     }
@@ -110,7 +94,7 @@ __global__ void k_w_from_t(float* __restrict__ W, const float* __restrict__ T, i
     GRID_STRIDE(q, n)
     {
         int i, j, k;
-        ft_coord(q, vdim, i, j, k);
+        hc_coord(q, vdim, i, j, k);
         if ((long)i * i + (long)j * j + (long)k * k < r2) W[q] = 1.f / fmaxf(fabsf(T[q]), 1e-6f);
     }
 }
@@ -222,7 +206,7 @@ __global__ void k_pad(float2* __restrict__ P, const float2* __restrict__ F, cons
     GRID_STRIDE(q, n)
     {
         int i, j, k;
-        ft_coord(q, vdim, i, j, k);
+        hc_coord(q, vdim, i, j, k);
         const float2 f = F[q];
         const float w = W[q];
         P[q] = ((long)i * i + (long)j * j + (long)k * k < r2) ? make_float2(f.x * w, f.y * w)
@@ -736,6 +720,16 @@ int col_pass(const Plans& p, float2* C, int vdim, bool inv, bool zAxis, hipStrea
 
 }  // namespace
 
+int thx::bind_plans(const Plans& p, void* work, hipStream_t s)
+{
+    for (hipfftHandle h : {p.c2r, p.r2c, p.r2cN, p.c2rX, p.r2cX}) {
+        if (!h) continue;
+        THX_FFT(hipfftSetWorkArea(h, work));
+        THX_FFT(hipfftSetStream(h, s));
+    }
+    return THX_OK;
+}
+
 int thx::c2r3d(const Plans& p, float2* C, float* rl, int vdim, hipStream_t s, int method)
 {
     if (!use_cols(p, method)) {
@@ -877,20 +871,7 @@ int solve_weights(PlanEntry* pe, float* T, int N, int pf, float a, float alpha, 
     float* oct = k.take<float>((size_t)(vdim / 2 + 1) * (vdim / 2 + 1) * (vdim / 2 + 1));
     unsigned* diff = k.take<unsigned>(64);
     void* fftWork = k.take<char>(work);
-    THX_FFT(hipfftSetWorkArea(pl.c2r, fftWork));
-    THX_FFT(hipfftSetWorkArea(pl.r2c, fftWork));
-    THX_FFT(hipfftSetStream(pl.c2r, s));
-    THX_FFT(hipfftSetStream(pl.r2c, s));
-    if (pl.cols) {
-        THX_FFT(hipfftSetWorkArea(pl.c2rX, fftWork));
-        THX_FFT(hipfftSetWorkArea(pl.r2cX, fftWork));
-        THX_FFT(hipfftSetStream(pl.c2rX, s));
-        THX_FFT(hipfftSetStream(pl.r2cX, s));
-    }
-    if (wantFT) {
-        THX_FFT(hipfftSetWorkArea(pl.r2cN, fftWork));
-        THX_FFT(hipfftSetStream(pl.r2cN, s));
-    }
+    THX_RET(thx::bind_plans(pl, fftWork, s));
     // the tabulated real-space kernel (float, as the reference's RFLOAT table)
     const std::vector<float>& htab = kernel_table(a, alpha);
     const float nf = (float)mkb_rl_r2(0.0, a, alpha);   // MKB_RL(0, a, alpha)
@@ -1067,11 +1048,7 @@ extern "C" int thx_fft3d(float* C, float* rl, int vdim, int inverse, int method,
     Plans& pl = pe->p;
     THX_CHECK_ARG(method != 2 || pl.cols, "thx_fft3d: no column passes for this vdim");
     THX_CHECK_ARG(workspace && wsBytes >= pl.work, "thx_fft3d: workspace too small");
-    for (hipfftHandle h : {pl.c2r, pl.r2c, pl.c2rX, pl.r2cX}) {
-        if (!h) continue;
-        THX_FFT(hipfftSetWorkArea(h, workspace));
-        THX_FFT(hipfftSetStream(h, s));
-    }
+    THX_RET(thx::bind_plans(pl, workspace, s));
     if (inverse)
         THX_RET(c2r3d(pl, reinterpret_cast<float2*>(C), rl, vdim, s, method));
     else

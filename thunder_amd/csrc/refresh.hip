@@ -49,6 +49,7 @@
 #include "common.h"
 #include "fft_lds.h"
 #include "fft_plans.h"
+#include "volume.h"
 
 namespace {
 
@@ -56,9 +57,6 @@ constexpr int RF_CT = 16;       // columns per tile of the column passes
 constexpr int RF_WAVES = 4;
 constexpr int RF_THREADS = 64 * RF_WAVES;
 constexpr int RF_RSTEP = RF_THREADS / RF_CT;
-
-// signed coordinate of a wrapped index
-THX_DEV int signed_idx(int a, int n) { return a < n / 2 ? a : a - n; }
 
 // softMask's weight of the source (1 - w, bg = 0) at distance u
 THX_DEV float soft_mask(float u, float r, float ew)
@@ -316,13 +314,6 @@ constexpr bool AUTO_PRUNED = true;
 
 bool route_pruned(int vdim, int method) { return method == 2 || (method == 0 && AUTO_PRUNED && pruned_ok(vdim)); }
 
-size_t ft_elems(int n) { return (size_t)n * n * (n / 2 + 1); }
-
-// hipFFT's work area is known only once a plan exists, and the workspace
-// query is host-only: reserve twice the transform's complex volume (the
-// 3D real plans of rocFFT take one) and check at the call.
-size_t fft_reserve(int box) { return 2 * ft_elems(box) * sizeof(float2); }
-
 struct Carved {
     float2* ftCopy = nullptr;   // fromFT: the C2R's input (hipFFT overwrites it)
     float* rl = nullptr;        // fromFT: the real-space map
@@ -341,16 +332,16 @@ Carved carve(void* ws, size_t cap, int N, int pf, bool pruned, bool fromFT)
     thx::Carver k(ws, cap);
     Carved c;
     if (fromFT) {
-        c.ftCopy = k.take<float2>(ft_elems(N));
+        c.ftCopy = k.take<float2>(thx::ft_elems(N));
         c.rl = k.take<float>((size_t)N * N * N);
-        c.workN = k.take<char>(fft_reserve(N));
+        c.workN = k.take<char>(thx::fft_reserve(N));
     }
     if (pruned) {
         c.X = k.take<float2>((size_t)N * N * H);
         c.Y = k.take<float2>((size_t)N * vdim * H);
     } else {
         c.pad = k.take<float>((size_t)vdim * vdim * vdim);
-        c.workV = k.take<char>(fft_reserve(vdim));
+        c.workV = k.take<char>(thx::fft_reserve(vdim));
     }
     c.bytes = k.off + 256;
     return c;
@@ -375,7 +366,7 @@ extern "C" int thx_ref_average(float* A, float* B, int N, int nK, float r, float
     THX_CHECK_ARG(std::isfinite(r) && std::isfinite(thres), "thx_ref_average: r / thres not finite");
     THX_CHECK_ARG(!(thres > 0.f) || (std::isfinite(ew) && ew > 0.f),
                   "thx_ref_average: the low-pass needs a finite ew > 0");
-    const long per = mode3d ? (long)ft_elems(N) : (long)N * (N / 2 + 1);
+    const long per = mode3d ? (long)thx::ft_elems(N) : (long)N * (N / 2 + 1);
     const long n = per * nK;
     hipLaunchKernelGGL(k_ref_average, dim3(thx::cdiv(n, 256)), dim3(256), 0, thx::as_stream(stream),
                        reinterpret_cast<float2*>(A), reinterpret_cast<float2*>(B), N, per, n, r, thres,
@@ -410,8 +401,8 @@ extern "C" int thx_projectee(const float* src, int fromFT, int N, int pf, float 
     const bool pruned = route_pruned(vdim, method);
     const Carved c = carve(workspace, wsBytes, N, pf, pruned, fromFT != 0);
     THX_CHECK_ARG(workspace && wsBytes >= c.bytes, "thx_projectee: workspace too small");
-    const size_t srcBytes = fromFT ? ft_elems(N) * sizeof(float2) : sizeof(float) * N * N * N;
-    const size_t dstBytes = ft_elems(vdim) * sizeof(float2);
+    const size_t srcBytes = fromFT ? thx::ft_elems(N) * sizeof(float2) : sizeof(float) * N * N * N;
+    const size_t dstBytes = thx::ft_elems(vdim) * sizeof(float2);
     THX_CHECK_ARG(!overlaps(dst, dstBytes, src, srcBytes), "thx_projectee: dst aliases src");
     THX_CHECK_ARG(!overlaps(dst, dstBytes, workspace, wsBytes), "thx_projectee: dst aliases the workspace");
     THX_CHECK_ARG(!alphaMask || !overlaps(dst, dstBytes, alphaMask, sizeof(float) * N * N * N),
@@ -424,9 +415,8 @@ extern "C" int thx_projectee(const float* src, int fromFT, int N, int pf, float 
         std::unique_lock<std::mutex> lk;
         thx::PlanEntry* pe = nullptr;
         THX_RET(thx::cached_plans(N, N / 2, s, &pe, lk));
-        THX_CHECK_ARG(pe->p.work <= fft_reserve(N), "thx_projectee: hipFFT's work area exceeds the reserve");
-        THX_FFT(hipfftSetWorkArea(pe->p.c2r, c.workN));
-        THX_FFT(hipfftSetStream(pe->p.c2r, s));
+        THX_CHECK_ARG(pe->p.work <= thx::fft_reserve(N), "thx_projectee: hipFFT's work area exceeds the reserve");
+        THX_RET(thx::bind_plans(pe->p, c.workN, s));
         THX_HIP(hipMemcpyAsync(c.ftCopy, src, srcBytes, hipMemcpyDeviceToDevice, s));
         THX_RET(thx::c2r3d(pe->p, c.ftCopy, c.rl, N, s, 1));
         rl = c.rl;
@@ -452,9 +442,8 @@ extern "C" int thx_projectee(const float* src, int fromFT, int N, int pf, float 
         }
 #undef THX_PRUNED
     }
-    THX_CHECK_ARG(pe->p.work <= fft_reserve(vdim), "thx_projectee: hipFFT's work area exceeds the reserve");
-    THX_FFT(hipfftSetWorkArea(pe->p.r2c, c.workV));
-    THX_FFT(hipfftSetStream(pe->p.r2c, s));
+    THX_CHECK_ARG(pe->p.work <= thx::fft_reserve(vdim), "thx_projectee: hipFFT's work area exceeds the reserve");
+    THX_RET(thx::bind_plans(pe->p, c.workV, s));
     hipLaunchKernelGGL(k_pad3, dim3(thx::cdiv(vdim, 64), thx::cdiv(vdim, 4), vdim), dim3(64, 4), 0, s, c.pad, rl, alphaMask, N, vdim,
                        rMask, edge, pv, interp, scale);
     THX_LAUNCH_CHECK();

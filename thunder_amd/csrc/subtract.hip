@@ -33,6 +33,7 @@
 // wave, the waves and then the blocks are added in index order by one thread.
 #include "common.h"
 #include "fft_plans.h"
+#include "volume.h"
 
 namespace {
 
@@ -230,9 +231,8 @@ __global__ void __launch_bounds__(RC_THREADS) k_centroid_partial(const float* __
     double a[4] = {0.0, 0.0, 0.0, 0.0};
     for (size_t q = blockIdx.x * (size_t)RC_THREADS + threadIdx.x; q < n3;
          q += (size_t)gridDim.x * RC_THREADS) {
-        const int ii = (int)(q % N), jj = (int)(q / N % N), kk = (int)(q / ((size_t)N * N));
-        const int i = ii < N / 2 ? ii : ii - N, j = jj < N / 2 ? jj : jj - N;
-        const int k = kk < N / 2 ? kk : kk - N;
+        const int i = signed_idx((int)(q % N), N), j = signed_idx((int)(q / N % N), N);
+        const int k = signed_idx((int)(q / ((size_t)N * N)), N);
         const double u = (double)map[q];
         a[0] += i * u;
         a[1] += j * u;
