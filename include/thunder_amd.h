@@ -853,6 +853,35 @@ int thx_expectation2d_ctf(const thx_expect_cfg* cfg, const thx_ctf_search_cfg* c
                           const int* iCol, const int* iRow, int nPxl, int nImg, double* rot,
                           double* trans, double* pR, double* pT, float* score, int* cls,
                           int* nPhaseOut, void* workspace, size_t wsBytes, thx_stream_t stream);
+/* thx_expectation_rank1st -- Particle::rank1st of every image of the call
+ * that last ran on `workspace`: the top particle calRank1st found in the
+ * image's last phase (the reseed's for a global search without phases; the
+ * particle of largest prior of the caller's state -- quat / pR, trans / pT,
+ * cs->d / cs->pD as passed in -- for a local search without phases).  The
+ * stopping rule leaves a retired image the top of the phase it stopped in.
+ * The top class is the cls the driver returns.
+ *   cfg, cs (NULL: no CTF search; only mLD is read), twoD (1: the 2d entry
+ *   points), nImg, nPxl, nOrd: as passed to that call -- the same workspace
+ *   plan is recomputed from them, so a value that differs makes the copies
+ *   read other slots of the workspace.  nOrd is the run's nOrd where it was
+ *   given a pxOrder and 0 where pxOrder was NULL; it is ignored with twoD = 1
+ *   (the 2D run has no pixel order).  wsBytes >= the plan on this buffer (the
+ *   matching workspace query is always enough).
+ *   topQuat nImg x 4 (MODE_2D: rows (cos, sin, 0, 0)), topTrans nImg x 2,
+ *   topD nImg (the top defocus factor; NULL unless cs), vari nImg x 6 (may be
+ *   NULL): {k1, k2, k3, s0, s1, sD} of the image's last calVari -- Particle::
+ *   vari's members, the reseed's floors included when no phase ran; 2D: k1 in
+ *   column 0; sD = 0 without cs.
+ * Device-to-device copies (and the memset of sD) on `stream`, nothing else:
+ * no synchronisation, capturable. The workspace must not have been handed to
+ * any other call between the run and this one (the driver keeps these values
+ * nowhere else); the run's nImg == 0 wrote nothing.  A null cfg / workspace,
+ * nImg < 0, nPxl <= 0, wsBytes below the plan or topD without cs is
+ * THX_ERR_ARG; nImg == 0 is a no-op. */
+int thx_expectation_rank1st(const thx_expect_cfg* cfg, const thx_ctf_search_cfg* cs, int twoD,
+                            int nImg, int nPxl, int nOrd, const void* workspace, size_t wsBytes,
+                            double* topQuat, double* topTrans, double* topD, double* vari,
+                            thx_stream_t stream);
 /* The perturbation mean of PARTICLE_ROT_MEAN_USING_STAT_PERTURB (inferACG's
  * principal axis, src/Geometry/DirectionalStat.cpp:93-145, 224-251; at most
  * acgIters fixed-point iterations): meanQ nImg x 4, iters (may be NULL) the
@@ -927,6 +956,45 @@ int thx_pf_top_by_weight(int nImg, int mR, const double* quat, const double* pR,
 int thx_pf_top_copy(int nImg, const double* src, long lds, const int* top, double* topQ,
                     const int* done, thx_stream_t stream);
 
+/* ------------------------------------------------- between two rounds ---
+ * What Optimiser::run does with the top particles between expectation() and
+ * the next round (src/Optimiser.cpp:3691-3833), on device.  Every pointer is
+ * a device pointer, FP64 unless said otherwise; nothing synchronises or
+ * allocates; nImg == 0 is a no-op.
+ *
+ * thx_rank1st_diff -- Particle::diffTopR / diffTopT / diffTopD / diffTopC
+ *   (src/Particle.cpp:2004-2038) of every image, one launch:
+ *     diffR[l] = 1 - |<prevQuat_l, topQuat_l>| over all 4 components (2D rows
+ *                (cos, sin, 0, 0) included),
+ *     diffT[l] = |prevTrans_l - topTrans_l|,  diffD[l] = |prevD_l - topD_l|,
+ *     sameC[l] = (prevCls_l == cls_l) -- 1 where the class did NOT change:
+ *                the reference's diffTopC returns the equality despite its
+ *                name,
+ *   then prev <- current in place.  Each group (current, prev, output) is
+ *   skipped when its three pointers are NULL; a group given in part is
+ *   THX_ERR_ARG.  cls / prevCls / sameC are int.
+ * thx_recentre -- Optimiser::reCentreImg (:6064-6090), with t = topTrans[l]:
+ *     offS[l] -= t;
+ *     imgFT[l] = oriFT[l] exp(-2 pi i (i rCol + j rRow)) on every stored
+ *                pixel ([idim][idim/2+1] Complex, Nyquist row and column
+ *                included), rCol / rRow = (float)offS[l] / idim from the
+ *                updated offset, the phase formed in FP32 like translate();
+ *     trans[l][0 .. mLT) -= t;  prevTrans[l] -= t;  topTrans[l] -= t (= 0).
+ *   imgFT (with oriFT), trans and prevTrans may each be NULL.  imgFT and
+ *   oriFT are distinct buffers.  Two launches: the state first, the image
+ *   pass after it reads the updated offS only.  idim even, <= 8192.
+ * thx_class_count -- count[cls[l]] += 1 for every image (count nK doubles the
+ *   caller zeroes; it accumulates over calls, batch after batch): the
+ *   numerator of refreshClassDistr (:5484-5516).  A class outside [0, nK) is
+ *   not counted and is no error. */
+int thx_rank1st_diff(int nImg, const double* topQuat, double* prevQuat, double* diffR,
+                     const double* topTrans, double* prevTrans, double* diffT,
+                     const double* topD, double* prevD, double* diffD, const int* cls,
+                     int* prevCls, int* sameC, thx_stream_t stream);
+int thx_recentre(int nImg, int idim, const float* oriFT, float* imgFT, double* topTrans,
+                 double* offS, int mLT, double* trans, double* prevTrans, thx_stream_t stream);
+int thx_class_count(int nImg, const int* cls, int nK, double* count, thx_stream_t stream);
+
 /* ------------------------------------------------------- noise model ---
  * What Optimiser::maximization (src/Optimiser.cpp:3405-3559) does next to
  * reconstructRef: allReduceSigma (:6395-6709), which makes the next round's
@@ -938,9 +1006,11 @@ int thx_pf_top_copy(int nImg, const double* src, long lds, const int* top, doubl
  *
  * Pose source: the reference takes Particle::rank1st per image.  These entry
  * points take one pose per image from the caller -- quat / rot [nImg][4 / 2],
- * trans [nImg][2], dF [nImg] (NULL = 1), cls [nImg] (NULL = class 0): the
- * draw the caller inserts with (sample 0 of the resampled set, the
- * reference's rand alternative at :6480) or its own top particle.
+ * trans [nImg][2], dF [nImg] (NULL = 1), cls [nImg] (NULL = class 0).  The
+ * driver exports rank1st: pass thx_expectation_rank1st's topQuat (2D: its
+ * first two columns), topTrans and topD with the cls the driver returned.
+ * (The reference's rand alternative at :6480 is the draw the caller inserts
+ * with.)
  *
  * thx_spectrum_pixels (host) -- the domain of powerSpectrum(dst, img, r)
  *   (src/Functions/Spectrum.cpp:161-190), listed shell by shell: the stored

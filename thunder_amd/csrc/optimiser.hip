@@ -1112,12 +1112,17 @@ int resample_launch(int nImg, bool shuffle, uint64_t seed, double* cdf, int* per
 // gather ancestors: dst[l][j][:] = src[l (or shared)][anc[l][j]][:]
 // keepDone: a done image's particles are copied unchanged (src and dst are
 // the two buffers of the phases' ping-pong, lds = nOut * width)
+// top / topV (optional): topV[l][:] = src[l (or shared)][top[l]][:], the top
+// particle's value (calRank1st), written by the threads of particle 0 for the
+// images not done -- the export of the rank1st values rides on this launch
 __global__ void __launch_bounds__(256) k_gather(int nImg, int nOut, int width,
                                                 const double* __restrict__ src, long lds,
                                                 int nIn, const int* __restrict__ anc,
                                                 double* __restrict__ dst,
                                                 const int* __restrict__ done = nullptr,
-                                                int keepDone = 0)
+                                                int keepDone = 0,
+                                                const int* __restrict__ top = nullptr,
+                                                double* __restrict__ topV = nullptr)
 {
     const long n = (long)nImg * nOut * width;
     for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < n;
@@ -1131,6 +1136,8 @@ __global__ void __launch_bounds__(256) k_gather(int nImg, int nOut, int width,
         }
         const int a = anc[lj];
         dst[q] = src[(size_t)l * lds + (size_t)a * width + c];
+        if (topV && lj == (long)l * nOut)
+            topV[(size_t)l * width + c] = src[(size_t)l * lds + (size_t)top[l] * width + c];
         (void)nIn;
     }
 }
@@ -1575,9 +1582,16 @@ __global__ void __launch_bounds__(1024) k_compact(int nImg, const int* __restric
 }
 
 // topQ[l] = the particle of largest prior pR (calRank1st on the caller's
-// state, for a local search that starts from it).
+// state, for a local search that starts from it).  topTv / topDv (optional):
+// the same for the translations (trans, pT) and the defocus factors (d, pD).
 __global__ void k_top_by_weight(int nImg, int mR, const double* __restrict__ quat,
-                                const double* __restrict__ pR, double* __restrict__ topQ)
+                                const double* __restrict__ pR, double* __restrict__ topQ,
+                                int mT = 0, const double* __restrict__ trans = nullptr,
+                                const double* __restrict__ pT = nullptr,
+                                double* __restrict__ topTv = nullptr, int mD = 0,
+                                const double* __restrict__ d = nullptr,
+                                const double* __restrict__ pD = nullptr,
+                                double* __restrict__ topDv = nullptr)
 {
     const int l = blockIdx.x * blockDim.x + threadIdx.x;
     if (l >= nImg) return;
@@ -1585,6 +1599,18 @@ __global__ void k_top_by_weight(int nImg, int mR, const double* __restrict__ qua
     for (int i = 1; i < mR; i++)
         if (pR[(size_t)l * mR + i] > pR[(size_t)l * mR + best]) best = i;
     for (int k = 0; k < 4; k++) topQ[4 * l + k] = quat[((size_t)l * mR + best) * 4 + k];
+    if (topTv) {
+        best = 0;
+        for (int i = 1; i < mT; i++)
+            if (pT[(size_t)l * mT + i] > pT[(size_t)l * mT + best]) best = i;
+        for (int k = 0; k < 2; k++) topTv[2 * l + k] = trans[((size_t)l * mT + best) * 2 + k];
+    }
+    if (topDv) {
+        best = 0;
+        for (int i = 1; i < mD; i++)
+            if (pD[(size_t)l * mD + i] > pD[(size_t)l * mD + best]) best = i;
+        topDv[l] = d[(size_t)l * mD + best];
+    }
 }
 
 // ---- defocus particles (PAR_D) of a CTF search, one image per GROUP lanes.
@@ -1753,6 +1779,9 @@ struct Plan {
     // CTF search: defocus precalculation, per-phase CTF table, D statistics
     float* freq; float* dfo; float* K1; float* K2; float* ctfD; float* wD;
     double* sdD; double* bestD; double* tmpD; int* topD;
+    // calRank1st's values beside topQ: _topT and, with a CTF search, _topD
+    // (read back by thx_expectation_rank1st)
+    double* topTv; double* topDv;
     size_t bytes;
 };
 
@@ -1850,6 +1879,10 @@ Plan plan(void* base, const thx_expect_cfg& c, int nImg, int nPxl, int nVisit, i
     // nImg) + 384 bytes, + up to 512 of alignment)
     p.stepOrd = k.take<int>(!twoD ? (size_t)nVisit + 32 : 0);
     p.stepPlan = k.take<int>(!twoD ? thx::step_plan_ints(nImg) : 0);
+    // the exported top translation / defocus, last: every buffer above stays
+    // where it was
+    p.topTv = k.take<double>((size_t)nImg * 2);
+    p.topDv = k.take<double>(on * nImg);
     p.bytes = k.off + 256;
     return p;
 }
@@ -2460,7 +2493,7 @@ struct Expect : ExpectArgs {
         THX_RET(resample({c.nT, c.mLT, gPT, 0, p.gWT, nK * c.nT, RNG_RESEED_T, p.anc, pT, p.topT,
                           clsSel, c.nT}));
         THX_LAUNCH(k_gather, dim3(1024), dim3(256), 0, s, nImg, c.mLT, 2, gTrans, 0L, c.nT,
-                   p.anc, trans, nullptr);
+                   p.anc, trans, nullptr, 0, p.topT, p.topTv);
         // calVari with the scan floors, beside phase 1's inferACG mean (both only
         // read the reseeded cloud); its symmetrise first, on the stream both read from
         return calvari(vari.s, quat, trans, RNG_SEED_ANCHOR, c.kMin, c.sMin, nullptr);
@@ -2473,7 +2506,8 @@ struct Expect : ExpectArgs {
         if (nK == 1 && !cls) THX_HIP(hipMemsetAsync(clsD, 0, sizeof(int) * nImg, s));
         THX_RET(calvari(s, quat, trans, RNG_SEED_ANCHOR, 0.0, 0.0, nullptr));
         THX_LAUNCH(k_top_by_weight, dim3(gOne), dim3(256), 0, s, nImg, c.mLR, quat, pR,
-                   p.topQ);
+                   p.topQ, c.mLT, trans, pT, p.topTv, mLD, cs ? cs->d : nullptr,
+                   cs ? cs->pD : nullptr, cs ? p.topDv : nullptr);
         // the rotation peak factor a fresh particle carries (resetPeakFactor,
         // src/Particle.cpp:1957-1962: PEAK_FACTOR_MIN); a global search sets it
         // in the reseed
@@ -2611,8 +2645,9 @@ struct Expect : ExpectArgs {
                    cq, (long)c.mLR * 4, p.topR, p.topQ, done);
         THX_RET(resample({c.mLT, c.mLT, pT, c.mLT, p.wT, c.mLT, RNG_RESAMPLE_T + phase, p.anc, pT,
                           p.topT, nullptr, 0, done}));
+        // with the top translation's value, from the pre-resample cloud
         THX_LAUNCH(k_gather, dim3(1024), dim3(256), 0, s, nImg, c.mLT, 2, (const double*)ct,
-                   (long)c.mLT * 2, c.mLT, p.anc, nt, done, 1);
+                   (long)c.mLT * 2, c.mLT, p.anc, nt, done, 1, p.topT, p.topTv);
         // the resampled clouds are current from here
         std::swap(cq, nq);
         std::swap(ct, nt);
@@ -2626,7 +2661,7 @@ struct Expect : ExpectArgs {
             THX_HIP(hipMemcpyAsync(p.tmpD, cs->d, sizeof(double) * nImg * mLD,
                                    hipMemcpyDeviceToDevice, s));
             THX_LAUNCH(k_gather, dim3(1024), dim3(256), 0, s, nImg, mLD, 1, p.tmpD,
-                       (long)mLD, mLD, p.anc, cs->d, done);
+                       (long)mLD, mLD, p.anc, cs->d, done, 0, p.topD, p.topDv);
         }
         return THX_OK;
     }
@@ -2712,6 +2747,40 @@ extern "C" size_t thx_expectation_ctf_workspace(const thx_expect_cfg* cfg,
 {
     if (!cfg || !cs || cs->mLD <= 0) return 0;
     return plan(nullptr, *cfg, nImg, nPxl, nOrd > 0 ? nOrd : nPxl, cs->mLD).bytes;
+}
+
+extern "C" int thx_expectation_rank1st(const thx_expect_cfg* cfg, const thx_ctf_search_cfg* cs,
+                                       int twoD, int nImg, int nPxl, int nOrd,
+                                       const void* workspace, size_t wsBytes, double* topQuat,
+                                       double* topTrans, double* topD, double* vari,
+                                       thx_stream_t stream)
+{
+    THX_CHECK_ARG(cfg && workspace, "thx_expectation_rank1st: null cfg or workspace");
+    THX_CHECK_ARG(nImg >= 0 && nPxl > 0, "thx_expectation_rank1st: bad sizes");
+    THX_CHECK_ARG(!cs || cs->mLD > 0, "thx_expectation_rank1st: bad CTF-search configuration");
+    THX_CHECK_ARG(cs || !topD, "thx_expectation_rank1st: topD needs a CTF search (cs)");
+    if (nImg == 0) return THX_OK;
+    THX_CHECK_ARG(topQuat && topTrans, "thx_expectation_rank1st: null output");
+    // the run's own carve (expectation_impl: nVisit = nOrd with a pixel order,
+    // nPxl without one and in MODE_2D): read-only here
+    const Plan p = plan(const_cast<void*>(workspace), *cfg, nImg, nPxl,
+                        !twoD && nOrd > 0 ? nOrd : nPxl, cs ? cs->mLD : 0, twoD != 0);
+    THX_CHECK_ARG(p.bytes <= wsBytes, "thx_expectation_rank1st: workspace smaller than the run's plan");
+    hipStream_t s = thx::as_stream(stream);
+    const size_t D = sizeof(double), n = (size_t)nImg;
+    THX_HIP(hipMemcpyAsync(topQuat, p.topQ, D * 4 * n, hipMemcpyDeviceToDevice, s));
+    THX_HIP(hipMemcpyAsync(topTrans, p.topTv, D * 2 * n, hipMemcpyDeviceToDevice, s));
+    if (topD) THX_HIP(hipMemcpyAsync(topD, p.topDv, D * n, hipMemcpyDeviceToDevice, s));
+    if (vari) {
+        // rows {k1, k2, k3, s0, s1, sD}
+        THX_HIP(hipMemcpy2DAsync(vari, 6 * D, p.kv, 3 * D, 3 * D, n, hipMemcpyDeviceToDevice, s));
+        THX_HIP(hipMemcpy2DAsync(vari + 3, 6 * D, p.sv, 2 * D, 2 * D, n, hipMemcpyDeviceToDevice, s));
+        if (cs)
+            THX_HIP(hipMemcpy2DAsync(vari + 5, 6 * D, p.sdD, D, D, n, hipMemcpyDeviceToDevice, s));
+        else
+            THX_HIP(hipMemset2DAsync(vari + 5, 6 * D, 0, D, n, s));
+    }
+    return THX_OK;
 }
 
 extern "C" int thx_expectation(const thx_expect_cfg* cfg, const float* vol,

@@ -7,6 +7,18 @@ expectation of an image batch through ``thx_expectation`` (C++ driver in
 csrc/optimiser.hip); ``Reconstructor`` inserts posterior samples into a
 device half-map through ``thx_insert3d``.  The half-map reduction across the
 ranks of one hemisphere is an RCCL all-reduce (``halfmap_allreduce``).
+
+The end of a round (src/Optimiser.cpp:3405-3419, 3691-3833), with the top
+particles the driver exports (Particle::rank1st)::
+
+    out = e.run(dat, ctf, sig)                       # expectation
+    cls, quat, trans, d, vari = e.rank1st()          # right after the run
+    nm.update(stack, vol, quat, trans, pf, offS, d, cls)   # nm: noise.NoiseModel
+    distr = round.class_distribution(cls, nK)        # refreshClassDistr
+    stats = round.refresh_variance(vari, two_d=False)
+    diffR, *_ = round.rank1st_change((cls, quat, trans, d), prev)
+    round.recentre(stack.oriFT, stack.imgFT, trans, offS, out[1], prev[2],
+                   remask=(r_mask, edge))
 """
 import ctypes
 import math
@@ -155,6 +167,7 @@ class Expectation:
                 self.cfg.nSymElem = len(q)
         self.mLR, self.mLT, self.nK = mLR, mLT, nK
         self.cs = CtfSearchCfg(mLD, ctf_refine_s, perturb_ctf, None, None, None)
+        self._last = None      # (workspace, nImg, cls) of the last run, for rank1st()
 
     def track_routes(self, n_phase):
         """Record the device route's kernel choice for the next runs' first
@@ -202,6 +215,7 @@ class Expectation:
         nph = torch.empty(nImg, dtype=torch.int32, device=dev)
         self.cs.attr, self.cs.d, self.cs.pD = attr.data_ptr(), d.data_ptr(), pD.data_ptr()
         ws = ops.workspace(self.workspace_bytes(nImg), dev)
+        self._last = (ws, nImg, cls)
         P = ops._ptr
         if self.two_d:
             check(lib().thx_expectation2d_ctf(ctypes.byref(self.cfg), ctypes.byref(self.cs),
@@ -251,6 +265,7 @@ class Expectation:
                    torch.empty(nImg, dtype=torch.int32, device=dev))
         quat, trans, pR, pT, score, cls, nph = out
         ws = ops.workspace(self.workspace_bytes(nImg), dev)
+        self._last = (ws, nImg, cls)
         P = ops._ptr
         if self.two_d:
             check(lib().thx_expectation2d(ctypes.byref(self.cfg), P(self.vol), P(self.gQuat),
@@ -266,6 +281,32 @@ class Expectation:
                                     P(quat), P(trans), P(pR), P(pT), P(score), P(cls), P(nph),
                                     P(ws), ws.numel(), ops._stream(dev)), "thx_expectation")
         return out
+
+    def rank1st(self):
+        """Particle::rank1st of every image of the last run / run_ctf
+        (thx_expectation_rank1st): (cls [n] int32, quat [n, 4] -- 2D: rows
+        (cos, sin, 0, 0) --, trans [n, 2], d [n] or None without a CTF search,
+        vari [n, 6] = k1 k2 k3 s0 s1 sD of the last calVari).  The values live
+        in the run's scratch (ops.workspace, shared by the calls of a stream):
+        read them right after the run, before any other call of this package
+        on the stream."""
+        if self._last is None:
+            raise RuntimeError("rank1st() follows run() / run_ctf()")
+        ws, nImg, cls = self._last
+        dev = self.dev
+        quat = torch.empty(nImg, 4, dtype=torch.float64, device=dev)
+        trans = torch.empty(nImg, 2, dtype=torch.float64, device=dev)
+        vari = torch.empty(nImg, 6, dtype=torch.float64, device=dev)
+        ctf = self.search == 2
+        d = torch.empty(nImg, dtype=torch.float64, device=dev) if ctf else None
+        P = ops._ptr
+        check(lib().thx_expectation_rank1st(ctypes.byref(self.cfg),
+                                            ctypes.byref(self.cs) if ctf else None,
+                                            int(self.two_d), nImg, self.px.n,
+                                            0 if self.two_d else len(self.px.order), P(ws),
+                                            ws.numel(), P(quat), P(trans), P(d), P(vari),
+                                            ops._stream(dev)), "thx_expectation_rank1st")
+        return cls, quat, trans, d, vari
 
 
 class PhaseTimer:
@@ -315,8 +356,9 @@ class Reconstructor:
 def cloud_mode(quat):
     """Medoid of each image's rotation cloud [nImg, m, 4] (max sum of squared
     cosines to the other particles).  Systematic resampling leaves particles
-    in ancestor order, so index 0 is not the top particle; this is the
-    estimate of Particle::rank1st without the weights."""
+    in ancestor order, so index 0 is not the top particle; this is an
+    estimate without the weights.  Particle::rank1st itself is
+    Expectation.rank1st()."""
     c = torch.einsum("lik,ljk->lij", quat, quat) ** 2
     return quat[torch.arange(quat.shape[0], device=quat.device), c.sum(-1).argmax(-1)]
 

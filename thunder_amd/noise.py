@@ -11,9 +11,9 @@ csrc/noise.hip.
     nm.update(stack, vol, quat, trans, offS=off, group=group)
 
 Pose source: one pose per image from the caller (quat [n, 4] or 2D rot
-[n, 2], trans [n, 2], dF [n], cls [n]) -- the draw it inserts with (sample 0
-of the resampled set) or its own top particle; the reference uses
-Particle::rank1st, which the expectation driver does not export.
+[n, 2], trans [n, 2], dF [n], cls [n]).  The reference uses
+Particle::rank1st: that is ``Expectation.rank1st()`` -- (cls, quat, trans, d,
+vari), read right after the run; in 2D pass ``quat[:, :2].contiguous()``.
 
 The sums over the hemisphere's images are all-reduced with
 ``hemisphere_group`` (a torch.distributed group), as stdN is in ingest.Stack.

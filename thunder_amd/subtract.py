@@ -12,7 +12,8 @@ csrc/subtract.hip.  3D only, as the reference.
     subtract.save_subtract(stack, vol, quat, trans, r, prefix, sym="C2", centre=centre)
 
 Pose source: one pose per image from the caller (quat [n, 4], trans [n, 2],
-dF [n], cls [n]), as in noise.py; the reference takes Particle::rank1st.
+dF [n], cls [n]), as in noise.py; the reference takes Particle::rank1st,
+which ``Expectation.rank1st()`` returns.
 
 The reference's flow around the subtraction (:4220-4330) is two passes, and
 the caller follows it with the calls this package already has -- there is no
