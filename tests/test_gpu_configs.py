@@ -21,7 +21,10 @@ marginals 1e-4 against a
 float64 normalisation of the kernel's own dvp (the dvp themselves are held
 to the oracle at 1e-5: one FP32 ulp of a dvp of magnitude |dvp| is
 |dvp| * 6e-8 in log-weight, and full-resolution dvp reach 1e4-1e5)."""
+import ctypes
 import math
+import os
+import re
 
 import numpy as np
 import pytest
@@ -263,6 +266,82 @@ def test_c3_driver_routes_bench_phases_to_ypair(c3):
     routes = e.track_routes(10)
     e.run(dat, ctf, sig)
     assert routes.cpu().tolist() == [2] * 10, routes.cpu().tolist()
+
+
+# ------------------------------------------------ one phase, five entry points
+def _phase_tile_rotations():
+    """RT of local.hip: the rotations one workgroup of the phase kernel covers."""
+    src = open(os.path.join(os.path.dirname(ops.__file__), "csrc", "local.hip")).read()
+    threads = int(re.search(r"constexpr int THREADS = (\d+);", src).group(1))
+    assert re.search(r"constexpr int NWAVE = THREADS / 64;", src)
+    assert re.search(r"constexpr int RT = 16 \* NWAVE;", src)
+    return 16 * (threads // 64)
+
+
+class _LocalSel(ctypes.Structure):      # thx_local_sel
+    _fields_ = [("active", ctypes.c_void_p), ("nActive", ctypes.c_void_p), ("cls", ctypes.c_void_p),
+                ("volStride", ctypes.c_longlong)]
+
+
+@pytest.mark.parametrize("tiles", [1, 2])
+def test_entry_points_of_one_phase_agree_bitwise(tiles):
+    """The entry points that describe the same phase run the same launches:
+    thx_local_phase (layout 0, pxOrder), thx_local_phase_sel with an all-null
+    sel and thx_local_phase_routed without a y-pair copy agree bit for bit on
+    wC, wR, wT, baseL and dvp, and so do thx_local_phase_routed on the whole
+    y-pair copy and thx_local_phase_routed_ball on the matching ball, which
+    also report the same route.  Box 32, 3 images, nT 3; nR 5 is one workgroup
+    per image with the fused epilogue, nR = RT + 1 two rotation tiles with the
+    likelihoods materialised and k_local_weights after them.  Each with a 1
+    degree cloud, whose patch boxes fit the LDS (route 0: the staged kernel),
+    and with unrelated rotations, under which a patch's copies span the ring's
+    whole shell and most boxes do not fit (route 1 box-less / 2 y-pair) --
+    with nR = RT + 1 the second tile's single rotation makes its boxes fit,
+    which is half the sampled patches, so the route stays staged at its 50 per
+    cent threshold and the other kernel, launched all the same, exits at entry.
+    The phases are run-to-run deterministic
+    (profiles/driver_refactor_identity.jsonl), hence equality, no tolerance."""
+    from bench import make_stack
+    from thunder_amd._lib import check, lib
+    N, pf, nImg, nT = 32, 2, 3, 3
+    nR = 5 if tiles == 1 else _phase_tile_rotations() + 1
+    vol = synth.projectee(synth.blob_volume(N, seed=7, device=DEV), pf)
+    px, dat, ctf, sig, *_ = make_stack(N, pf, 12, 1, nImg, DEV, seed=61, vol=vol)
+    yp, R = ops.volume_ypair(vol), ops.ypair_ball_radius(px)
+    ball = ops.volume_ypair_ball(vol, R)
+    rng = np.random.default_rng(14)
+    trans = T(rng.standard_normal((nImg, nT, 2)))
+    pC, pR, pT = T(np.ones(nImg)), T(np.full((nImg, nR), 1.0 / nR)), T(np.full((nImg, nT), 1.0 / nT))
+    ws = ops.workspace(lib().thx_local_phase_workspace(nImg, nR, nT, len(px.order)), DEV)
+    p, sel = ops._ptr, _LocalSel(None, None, None, 0)
+
+    def run(fn, lead, quat, routed):
+        out = [torch.full(sh, float("nan"), dtype=torch.float32, device=DEV)
+               for sh in ((nImg,), (nImg, nR), (nImg, nT), (nImg,), (nImg, nR, nT))]
+        route = torch.full((1,), -2, dtype=torch.int32, device=DEV)
+        check(getattr(lib(), fn)(
+            *lead, pf * N, pf, p(quat), nR, p(trans), nT, p(pC), p(pR), p(pT), p(dat), p(ctf), p(sig),
+            p(px.d_iCol), p(px.d_iRow), p(px.d_order), len(px.order), px.n, px.idim, nImg,
+            *(p(x) for x in out), *((p(route),) if routed else ()), p(ws), ws.numel(),
+            ops._stream(DEV)), fn)
+        assert all(bool(torch.isfinite(x).all()) for x in out), fn
+        return [x.view(torch.int32) for x in out], int(route.item())
+
+    def same(a, b):
+        return all(torch.equal(x, y) for x, y in zip(a, b))
+
+    routes = []
+    for quat in (T(synth.clustered_quaternions(nImg, nR, 1.0, rng)),
+                 T(synth.uniform_quaternions(nImg * nR, rng).reshape(nImg, nR, 4))):
+        plain, _ = run("thx_local_phase", (p(vol), 0), quat, False)
+        by_sel, _ = run("thx_local_phase_sel", (ctypes.addressof(sel), p(vol), 0), quat, False)
+        routed, r0 = run("thx_local_phase_routed", (None, p(vol), None), quat, True)
+        assert same(plain, by_sel) and same(plain, routed)
+        whole, r1 = run("thx_local_phase_routed", (None, p(vol), p(yp)), quat, True)
+        compact, r2 = run("thx_local_phase_routed_ball", (None, p(vol), p(ball), R), quat, True)
+        assert same(whole, compact) and r1 == r2
+        routes.append((r0, r1))
+    assert routes == [(0, 0), (1, 2) if tiles == 1 else (0, 0)], routes
 
 
 # ---------------------------------------------------------------------- C2

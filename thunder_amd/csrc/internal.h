@@ -26,24 +26,42 @@ float scan_guard_default();
 // ---- local.hip: the 3D phase and what the driver needs around it
 int launch_local_weights(const float* dvp, int nR, int nT, const double* pC, const double* pR,
                          const double* pT, float* wC, float* wR, float* wT, float* baseL, int nImg,
-                         hipStream_t s, const int* act = nullptr, const int* nAct = nullptr);
+                         hipStream_t s, const int* act, const int* nAct);
 int launch_local_weights_d(const float* dvp, int nR, int nT, int nD, const double* pC,
                            const double* pR, const double* pT, const double* pD, float* wC,
                            float* wR, float* wT, float* wD, float* baseL, int nImg, hipStream_t s,
-                           const int* act = nullptr, const int* nAct = nullptr);
-// evBeg / evEnd (may be NULL): recorded around the phase kernel; dvp (may be
-// NULL): receives the materialised likelihoods
-int local_phase_impl(const thx_local_sel* sel, hipEvent_t evBeg, hipEvent_t evEnd,
-                     const float* vol, int volLayout, int vdim, int pf, const double* quat, int nR,
-                     const double* trans, int nT, const double* pC, const double* pR,
-                     const double* pT, const float* dat, const float* ctf, const float* sigRcp,
-                     const int* iCol, const int* iRow, const int* pxOrder, int nOrd, int nPxl,
-                     int idim, int nImg, float* wC, float* wR, float* wT, float* baseL, float* dvp,
-                     void* workspace, size_t wsBytes, thx_stream_t stream, int nD = 0,
-                     const double* pD = nullptr, float* wD = nullptr,
-                     const float* ypair = nullptr, int* routeOut = nullptr,
-                     const int* const* routeSample = nullptr, int ypairR = 0,
-                     const int* const* stepPlan = nullptr);
+                           const int* act, const int* nAct);
+// One 3D phase, as the C-ABI entry points and the expectation driver describe it.
+struct LocalPhase {
+    // volume in volLayout (0 half-complex, 1 cells, 2 y-pair); a routed phase's
+    // y-pair copy: the whole one, or the compact ball of radius ypairR > 0
+    const float *vol = nullptr, *ypair = nullptr;
+    int volLayout = 0, vdim = 0, pf = 0, ypairR = 0;
+    // cloud and priors.  nD = 0: no CTF search; nD >= 1: CTF search over nD
+    // defocus samples (ctf = ctfD[nImg][nD][nPxl], priors pD[nImg][nD], marginal wD)
+    const double *quat = nullptr, *trans = nullptr;
+    int nR = 0, nT = 0, nD = 0;
+    const double *pC = nullptr, *pR = nullptr, *pT = nullptr, *pD = nullptr;
+    const float *dat = nullptr, *ctf = nullptr, *sigRcp = nullptr;
+    int nPxl = 0, idim = 0, nImg = 0;
+    // pixel set and its visiting order (pxOrder NULL: set order)
+    const int *iCol = nullptr, *iRow = nullptr, *pxOrder = nullptr;
+    int nOrd = 0;
+    // outputs; dvp (may be NULL) receives the materialised likelihoods
+    float *wC = nullptr, *wR = nullptr, *wT = nullptr, *wD = nullptr, *baseL = nullptr, *dvp = nullptr;
+    const thx_local_sel* sel = nullptr;     // selection (may be NULL)
+    // driver extras, all optional.  evBeg / evEnd: recorded around the phase
+    // kernel; routeOut (device): the routed phase's kernel choice; routeSample =
+    // {list, count}: the images the route samples instead of the active list;
+    // stepPlan = {order, plan} of step_plan_build instead of one built here
+    hipEvent_t evBeg = nullptr, evEnd = nullptr;
+    int* routeOut = nullptr;
+    const int *const *routeSample = nullptr, *const *stepPlan = nullptr;
+    void* workspace = nullptr;
+    size_t wsBytes = 0;
+    thx_stream_t stream = nullptr;
+};
+int local_phase_impl(const LocalPhase& ph);
 size_t local_phase_workspace_planned(int nImg, int nR, int nT, int nVisit);
 size_t step_plan_ints(int nImg);
 bool step_plan_build(const int* pxOrder, int nOrd, const float* dat, const float* sigRcp, int nPxl,

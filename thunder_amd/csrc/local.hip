@@ -295,6 +295,8 @@ THX_DEV float quad_sum(float v)
 enum { LAYOUT_FT = 0, LAYOUT_CELLS = 1, LAYOUT_YPAIR2 = 2 };
 // layouts gathered quad-cooperatively (no LDS boxes, no patch records)
 constexpr bool coop_layout(int l) { return l == LAYOUT_CELLS; }
+// kernels without an LDS box: the cell and y-pair layouts, and STAGE = false
+constexpr bool boxless(int l, bool stage) { return coop_layout(l) || l == LAYOUT_YPAIR2 || !stage; }
 
 // Patch record (k_patch_boxes -> k_local_fused): layout in patch.h.
 struct Rec {
@@ -853,9 +855,10 @@ THX_DEV float2 interp_box(const float2* __restrict__ box, int nx, int sp, int of
 // A CS workgroup covers NCT column tiles of 16 (up to 96 (t, d) columns), so
 // the projection -- the expensive part -- is gathered once for all of them;
 // each step then issues 4 NCT MFMAs against NCT accumulators.
-// the big-box kernel from a pixel ring of BIGBOX_MIN_R projectee voxels on
-// (C5 full resolution; profiles/r02_local_bigbox_ab.jsonl)
+// the big-box kernel from a pixel ring of BIGBOX_MIN_R projectee voxels on, its
+// outer radius pf sqrt(2 nPxl / pi) (C5 full resolution; profiles/r02_local_bigbox_ab.jsonl)
 constexpr double BIGBOX_MIN_R = 300;
+inline bool big_box(int pf, int nPxl) { return pf * std::sqrt(2.0 * nPxl / M_PI) >= BIGBOX_MIN_R; }
 // box-less and y-pair kernels: 6 waves per SIMD (4 / 5 / 8 measured slower,
 // profiles/r03_nobox_waves_ab.jsonl, r04_pair_waves_ball_ab.jsonl)
 constexpr int NOBOX_WAVES = 6;
@@ -866,7 +869,7 @@ template <int LAYOUT, bool CS = false, int NCT = 1, bool BIGBOX = false, bool ST
 // no LDS box (cell layout, or STAGE = false): no box prefetch registers, so
 // 6 waves per SIMD (three workgroups per CU) for the L2 gathers
 __global__ void __launch_bounds__(THREADS)
-__attribute__((amdgpu_waves_per_eu((CS || BIGBOX) ? 2 : (coop_layout(LAYOUT) || LAYOUT == LAYOUT_YPAIR2 || !STAGE) ? NOBOX_WAVES : 4)))
+__attribute__((amdgpu_waves_per_eu((CS || BIGBOX) ? 2 : boxless(LAYOUT, STAGE) ? NOBOX_WAVES : 4)))
 k_local_fused(const float2* __restrict__ vol,
                                                             int vdim, int pf,
                                                             const double* __restrict__ quat,
@@ -902,7 +905,7 @@ k_local_fused(const float2* __restrict__ vol,
                                        : STAGE ? ROUTE_STAGED : ROUTE_NOBOX)) return;
     // box-less kernels with a step plan: `order` is the step-compacted order
     // (k_step_compact), its length is on the device, A_l in the plan
-    const bool planned = (coop_layout(LAYOUT) || LAYOUT == LAYOUT_YPAIR2 || !STAGE) && plan;
+    const bool planned = boxless(LAYOUT, STAGE) && plan;
     if (planned) nVisit = plan[0];
     int l = blockIdx.x;
     if (act) {
@@ -921,14 +924,14 @@ k_local_fused(const float2* __restrict__ vol,
     // STAGE = false: every patch gathered from L2 (no box, no records)
     // the pair form of the y-pair gather (two lanes per sample)
     constexpr bool PAIR = LAYOUT == LAYOUT_YPAIR2;
-    constexpr bool NOBOX = COOP || PAIR || !STAGE;
+    constexpr bool NOBOX = boxless(LAYOUT, STAGE);
     auto staged = [](const Rec& r) { return !NOBOX && r.v[10] <= BOXC; };
     constexpr int NC = NCT * TT;   // columns per workgroup
     // box-less kernels stage PP patches' image tiles per barrier pair (fewer
     // barriers, 4 PP independent steps between them); CS keeps one.  PP 2:
     // full-res cells -2.5 %, the bench's phases unchanged; PP 4 needs two
     // image-tile elements per thread and spills (profiles/r03_nobox_pp_ab.jsonl)
-    constexpr int PP = (coop_layout(LAYOUT) || PAIR || !STAGE) && !CS ? 2 : 1;
+    constexpr int PP = NOBOX && !CS ? 2 : 1;
     constexpr int PKC = PP * KC;                        // pixels per iteration
     constexpr int NE = (PKC * TT + THREADS - 1) / THREADS;   // image-tile elements per thread
     const int r0 = blockIdx.y * RT, t0 = blockIdx.z * NC;
@@ -1699,24 +1702,17 @@ static int step_plan_launch(const int* pxOrder, int nOrd, const float* dat, cons
     return THX_OK;
 }
 
-// nD = 0: the phase without CTF search; nD >= 1: CTF search over nD defocus
-// samples (ctf = ctfD[nImg][nD][nPxl], priors pD[nImg][nD], marginal wD).
 // Behind the C-ABI entry points below and, with the phase kernel's event pair,
 // the expectation driver.
-int thx::local_phase_impl(const thx_local_sel* sel, hipEvent_t evBeg, hipEvent_t evEnd,
-                          const float* vol, int volLayout, int vdim,
-                          int pf, const double* quat, int nR, const double* trans, int nT,
-                          const double* pC, const double* pR, const double* pT, const float* dat,
-                          const float* ctf, const float* sigRcp, const int* iCol, const int* iRow,
-                          const int* pxOrder, int nOrd, int nPxl, int idim, int nImg, float* wC,
-                          float* wR, float* wT, float* baseL, float* dvp, void* workspace,
-                          size_t wsBytes, thx_stream_t stream, int nD, const double* pD, float* wD,
-                          const float* ypair, int* routeOut, const int* const* routeSample,
-                          int ypairR, const int* const* stepPlan)
+int thx::local_phase_impl(const LocalPhase& ph)
 {
-    THX_CHECK_ARG(nR > 0 && nT > 0 && nPxl > 0 && nImg >= 0 && vdim > 0 && pf > 0 && nD >= 0,
+    const int volLayout = ph.volLayout, nR = ph.nR, nT = ph.nT, nD = ph.nD, nPxl = ph.nPxl,
+              nImg = ph.nImg, nOrd = ph.nOrd;
+    const int* const pxOrder = ph.pxOrder;
+    const thx_local_sel* const sel = ph.sel;
+    THX_CHECK_ARG(nR > 0 && nT > 0 && nPxl > 0 && nImg >= 0 && ph.vdim > 0 && ph.pf > 0 && nD >= 0,
                   "thx_local_phase: bad sizes");
-    THX_CHECK_ARG(!nD || (pD && wD && (long)nT * nD <= LOCAL_D_MAXCOL),
+    THX_CHECK_ARG(!nD || (ph.pD && ph.wD && (long)nT * nD <= LOCAL_D_MAXCOL),
                   "thx_local_phase_d: needs pD, wD and nT * nD <= 1024");
     const int nCol = nD ? nT * nD : nT;
     THX_CHECK_ARG(volLayout >= 0 && volLayout <= 2, "thx_local_phase: volLayout must be 0 .. 2");
@@ -1732,155 +1728,156 @@ int thx::local_phase_impl(const thx_local_sel* sel, hipEvent_t evBeg, hipEvent_t
     THX_CHECK_ARG(!act == !nAct, "thx_local_phase_sel: active and nActive go together");
     THX_CHECK_ARG(!cls || (sel->volStride > 0), "thx_local_phase_sel: cls needs a volStride");
     if (nImg == 0) return THX_OK;
-    THX_CHECK_ARG(!ypair || (volLayout == LAYOUT_FT && pxOrder && !nD),
+    THX_CHECK_ARG(!ph.ypair || (volLayout == LAYOUT_FT && pxOrder && !nD),
                   "thx_local_phase_routed: a y-pair copy goes with the half-complex layout and pxOrder");
     const int nVisit = pxOrder ? nOrd : nPxl;
-    // big LDS boxes for large full-resolution pixel sets: the ring's outer
-    // radius in projectee voxels, pf sqrt(2 nPxl / pi), past BIGBOX_MIN_R
-    const bool big = pf * std::sqrt(2.0 * nPxl / M_PI) >= BIGBOX_MIN_R;
+    const bool big = big_box(ph.pf, nPxl);
     // the staged / box-less (or y-pair) route of a half-complex phase, chosen
     // on the device from a sample of the patch records (route_pick)
-    const bool routed = volLayout == LAYOUT_FT && !nD && !big;
+    const bool routed = phase_routed(volLayout, ph.pf, nPxl, nD);
     // a phase that runs, or may be routed to, a box-less kernel takes a step
     // plan: the caller's (stepPlan = {order, plan} of thx::step_plan_build: the
     // driver builds one per call, for all its phases) or one built here in the
     // workspace (two small launches, no host round trip).  The staged kernel,
     // the records and the route's sample keep pxOrder.
-    const bool nobox = routed || coop_layout(volLayout) || volLayout == LAYOUT_YPAIR2;
-    const bool compact = nobox && pxOrder && step_compaction_on();
-    const bool ownPlan = compact && !stepPlan;
-    THX_CHECK_ARG(workspace && wsBytes >= (ownPlan ? thx_local_phase_workspace(nImg, nR, nCol, nVisit)
-                                                   : local_phase_workspace_planned(nImg, nR, nCol, nVisit)),
+    const bool nobox = boxless(volLayout, true);    // the layout's own kernel has no boxes
+    const bool compact = (routed || nobox) && pxOrder && step_compaction_on();
+    const bool ownPlan = compact && !ph.stepPlan;
+    THX_CHECK_ARG(ph.workspace &&
+                      ph.wsBytes >= (ownPlan ? thx_local_phase_workspace(nImg, nR, nCol, nVisit)
+                                             : local_phase_workspace_planned(nImg, nR, nCol, nVisit)),
                   "thx_local_phase: workspace too small");
-    thx::Carver ws(workspace, wsBytes);
-    float* d = dvp ? dvp : ws.take<float>((size_t)nImg * nR * nCol);
+    thx::Carver ws(ph.workspace, ph.wsBytes);
+    float* d = ph.dvp ? ph.dvp : ws.take<float>((size_t)nImg * nR * nCol);
     int* rec = ws.take<int>(rec_bytes(nImg, nR, nVisit) / sizeof(int));
     int* route = ws.take<int>(64);
-    hipStream_t s = thx::as_stream(stream);
+    hipStream_t s = thx::as_stream(ph.stream);
     const unsigned nRT = thx::cdiv(nR, RT);
-    const int* cOrd = compact && stepPlan ? stepPlan[0] : nullptr;
-    const int* plan = compact && stepPlan ? stepPlan[1] : nullptr;
+    const int* cOrd = compact && ph.stepPlan ? ph.stepPlan[0] : nullptr;
+    const int* plan = compact && ph.stepPlan ? ph.stepPlan[1] : nullptr;
     if (ownPlan) {
         int* o = ws.take<int>((size_t)nVisit + 32);
         int* pl = ws.take<int>((size_t)PLAN_A + nImg);
-        THX_RET(step_plan_launch(pxOrder, nOrd, dat, sigRcp, nPxl, nImg, nD, act, nAct, o, pl, s));
+        THX_RET(step_plan_launch(pxOrder, nOrd, ph.dat, ph.sigRcp, nPxl, nImg, nD, act, nAct, o, pl, s));
         cOrd = o;
         plan = pl;
     }
     const int* nbOrder = plan ? cOrd : pxOrder;     // the box-less kernels' order
+    auto boxes = [&](unsigned nImgGrid, const int* a, const int* nA, int* rt, int routeMode) {
+        hipLaunchKernelGGL(k_patch_boxes, dim3(nImgGrid * nRT), dim3(64 * PB_WAVES), 0, s, ph.quat, nR,
+                           ph.iCol, ph.iRow, pxOrder, nVisit, ph.pf, ph.vdim, rec, a, nA, rt, routeMode);
+    };
     if (routed) {
         THX_HIP(hipMemsetAsync(route, 0, 2 * sizeof(int), s));
-        THX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(route + 2), ypair ? 1 : 0, 1, s));
+        THX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(route + 2), ph.ypair ? 1 : 0, 1, s));
         // the route's sample: every ROUTE_SAMPLE-th entry of the active list,
         // or of the list the caller names (routeSample = {list, count}, both
         // null = every image in index order), so that a reordered active list
         // does not change the sample and with it the kernel
-        const int* sAct = routeSample ? routeSample[0] : act;
-        const int* sNAct = routeSample ? routeSample[1] : nAct;
-        hipLaunchKernelGGL(k_patch_boxes, dim3((unsigned)thx::cdiv(nImg, ROUTE_SAMPLE) * nRT),
-                           dim3(64 * PB_WAVES), 0, s, quat, nR, iCol, iRow, pxOrder, nVisit, pf, vdim,
-                           rec, sAct, sNAct, route, 1);
+        boxes(thx::cdiv(nImg, ROUTE_SAMPLE), ph.routeSample ? ph.routeSample[0] : act,
+              ph.routeSample ? ph.routeSample[1] : nAct, route, 1);
         THX_LAUNCH_CHECK();
-        if (routeOut) {
-            hipLaunchKernelGGL(k_route_out, dim3(1), dim3(64), 0, s, route, routeOut);
+        if (ph.routeOut) {
+            hipLaunchKernelGGL(k_route_out, dim3(1), dim3(64), 0, s, route, ph.routeOut);
             THX_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(k_patch_boxes, dim3((unsigned)nImg * nRT), dim3(64 * PB_WAVES), 0, s, quat,
-                           nR, iCol, iRow, pxOrder, nVisit, pf, vdim, rec, act, nAct, route, 2);
+        boxes(nImg, act, nAct, route, 2);
         THX_LAUNCH_CHECK();
-    } else if (!coop_layout(volLayout) && volLayout != LAYOUT_YPAIR2) {   // no boxes for these
-        if (routeOut) THX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(routeOut), -1, 1, s));
-        hipLaunchKernelGGL(k_patch_boxes, dim3((unsigned)nImg * nRT), dim3(64 * PB_WAVES), 0, s, quat,
-                           nR, iCol, iRow, pxOrder, nVisit, pf, vdim, rec, act, nAct, nullptr, 0);
+    } else if (!nobox) {
+        if (ph.routeOut)
+            THX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ph.routeOut), -1, 1, s));
+        boxes(nImg, act, nAct, nullptr, 0);
         THX_LAUNCH_CHECK();
     }
-    dim3 grid(nImg, thx::cdiv(nR, RT), thx::cdiv(nCol, TT));
-    const long vs = cls ? (long)sel->volStride : 0L;
-    if (evBeg) THX_HIP(hipEventRecord(evBeg, s));
-    if (nD) {
-        // all (t, d) columns of a workgroup in NCT tiles (one gather of the
-        // projection), up to 96 per workgroup
-        const int need = (int)thx::cdiv(nCol, TT);
-        const int nct = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 6;
-        auto pick = [&](auto c1, auto c2, auto c4, auto c6) {
-            return nct == 1 ? c1 : nct == 2 ? c2 : nct == 4 ? c4 : c6;
-        };
-        auto kern = volLayout == LAYOUT_CELLS
-                        ? pick(k_local_fused<LAYOUT_CELLS, true, 1>, k_local_fused<LAYOUT_CELLS, true, 2>,
-                               k_local_fused<LAYOUT_CELLS, true, 4>, k_local_fused<LAYOUT_CELLS, true, 6>)
-                        : pick(k_local_fused<LAYOUT_FT, true, 1>, k_local_fused<LAYOUT_FT, true, 2>,
-                               k_local_fused<LAYOUT_FT, true, 4>, k_local_fused<LAYOUT_FT, true, 6>);
-        grid.z = thx::cdiv(nCol, TT * nct);
-        hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s, reinterpret_cast<const float2*>(vol),
-                           vdim, pf, quat, nR, trans, nCol, reinterpret_cast<const float2*>(dat),
-                           ctf, sigRcp, iCol, iRow, coop_layout(volLayout) ? nbOrder : pxOrder, nVisit,
-                           nPxl, idim, rec, d, act, nAct, cls, vs, nD, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, nullptr, 0,
-                           coop_layout(volLayout) ? plan : nullptr);
-        THX_LAUNCH_CHECK();
-        if (evEnd) THX_HIP(hipEventRecord(evEnd, s));
-        return launch_local_weights_d(d, nR, nT, nD, pC, pR, pT, pD, wC, wR, wT, wD, baseL, nImg, s,
-                                      act, nAct);
-    }
-    auto kern =
-        volLayout == LAYOUT_YPAIR2 ? k_local_fused<LAYOUT_YPAIR2>
-        : volLayout == LAYOUT_CELLS
-            ? (big ? k_local_fused<LAYOUT_CELLS, false, 1, true> : k_local_fused<LAYOUT_CELLS>)
-            : (big ? k_local_fused<LAYOUT_FT, false, 1, true> : k_local_fused<LAYOUT_FT>);
+    // the kernel of an unrouted phase.  CTF search: all (t, d) columns of a
+    // workgroup in NCT tiles (one gather of the projection), up to 96 per workgroup
+    using Kern = decltype(&k_local_fused<LAYOUT_FT>);
+    static const int NCTS[4] = {1, 2, 4, 6};
+    static const Kern searchKern[2][4] = {   // [cells][NCT]
+        {k_local_fused<LAYOUT_FT, true, 1>, k_local_fused<LAYOUT_FT, true, 2>,
+         k_local_fused<LAYOUT_FT, true, 4>, k_local_fused<LAYOUT_FT, true, 6>},
+        {k_local_fused<LAYOUT_CELLS, true, 1>, k_local_fused<LAYOUT_CELLS, true, 2>,
+         k_local_fused<LAYOUT_CELLS, true, 4>, k_local_fused<LAYOUT_CELLS, true, 6>}};
+    static const Kern plainKern[3][2] = {    // [layout][big]
+        {k_local_fused<LAYOUT_FT>, k_local_fused<LAYOUT_FT, false, 1, true>},
+        {k_local_fused<LAYOUT_CELLS>, k_local_fused<LAYOUT_CELLS, false, 1, true>},
+        {k_local_fused<LAYOUT_YPAIR2>, k_local_fused<LAYOUT_YPAIR2>}};
+    const int need = (int)thx::cdiv(nCol, TT), ti = !nD || need <= 1 ? 0 : need <= 2 ? 1 : need <= 4 ? 2 : 3;
+    const Kern kern = nD ? searchKern[volLayout == LAYOUT_CELLS][ti] : plainKern[volLayout][big];
+    const dim3 grid(nImg, nRT, thx::cdiv(nCol, TT * NCTS[ti]));
     // one workgroup per image (nR <= 128, nT <= 16, the phases' 125 x 9):
     // the normalisation runs in the kernel's epilogue and dvp is only written
-    // when the caller asks for it
-    const bool fuse = grid.y == 1 && grid.z == 1;
-    // boxless: the kernel has no LDS boxes and takes the step plan
-    auto launch = [&](auto k, const int* rt, bool boxless) {
-        hipLaunchKernelGGL(k, grid, dim3(THREADS), 0, s, reinterpret_cast<const float2*>(vol), vdim,
-                           pf, quat, nR, trans, nT, reinterpret_cast<const float2*>(dat), ctf, sigRcp,
-                           iCol, iRow, boxless ? nbOrder : pxOrder, nVisit, nPxl, idim, rec,
-                           fuse ? dvp : d, act, nAct, cls, vs, 1, pC, pR, pT, fuse ? wC : nullptr,
-                           fuse ? wR : nullptr, fuse ? wT : nullptr, fuse ? baseL : nullptr, rt, 0,
-                           boxless ? plan : nullptr);
+    // when the caller asks for it (never with CTF search, which takes no priors)
+    const bool fuse = !nD && grid.y == 1 && grid.z == 1;
+    const double *pC = nD ? nullptr : ph.pC, *pR = nD ? nullptr : ph.pR, *pT = nD ? nullptr : ph.pT;
+    float *wC = fuse ? ph.wC : nullptr, *wR = fuse ? ph.wR : nullptr, *wT = fuse ? ph.wT : nullptr,
+          *baseL = fuse ? ph.baseL : nullptr, *out = fuse ? ph.dvp : d;
+    // v: the copy k gathers from, stride: between its classes; nb: k has no LDS
+    // boxes and takes the step plan; ballR > 0: v is the compact y-pair ball
+    auto launch = [&](Kern k, const float* v, long stride, bool nb, const int* rt, int ballR) {
+        hipLaunchKernelGGL(k, grid, dim3(THREADS), 0, s, reinterpret_cast<const float2*>(v), ph.vdim,
+                           ph.pf, ph.quat, nR, ph.trans, nCol, reinterpret_cast<const float2*>(ph.dat),
+                           ph.ctf, ph.sigRcp, ph.iCol, ph.iRow, nb ? nbOrder : pxOrder, nVisit, nPxl,
+                           ph.idim, rec, out, act, nAct, cls, stride, nD ? nD : 1, pC, pR, pT, wC, wR,
+                           wT, baseL, rt, ballR, nb ? plan : nullptr);
     };
+    const long vs = cls ? (long)sel->volStride : 0L;
+    if (ph.evBeg) THX_HIP(hipEventRecord(ph.evBeg, s));
     if (routed) {
         // two launches, the staged kernel and (with a y-pair copy) the pair-form
         // y-pair kernel or (without) the box-less half-complex one; the kernel
         // the route did not pick exits at entry
-        launch(k_local_fused<LAYOUT_FT, false, 1, false, true>, route, false);
-        if (ypair) {
-            hipLaunchKernelGGL(k_local_fused<LAYOUT_YPAIR2>, grid, dim3(THREADS), 0, s,
-                               reinterpret_cast<const float2*>(ypair), vdim, pf, quat, nR, trans, nT,
-                               reinterpret_cast<const float2*>(dat), ctf, sigRcp, iCol, iRow, nbOrder,
-                               nVisit, nPxl, idim, rec, fuse ? dvp : d, act, nAct, cls,
-                               cls ? (ypairR > 0 ? 2L * (long)thx_ypair_ball_elems(ypairR) : 2 * vs) : 0L, 1,
-                               pC, pR, pT, fuse ? wC : nullptr, fuse ? wR : nullptr,
-                               fuse ? wT : nullptr, fuse ? baseL : nullptr, route, ypairR, plan);
+        launch(k_local_fused<LAYOUT_FT, false, 1, false, true>, ph.vol, vs, false, route, 0);
+        if (ph.ypair) {
+            const long ys = ph.ypairR > 0 ? 2L * (long)thx_ypair_ball_elems(ph.ypairR) : 2 * vs;
+            launch(k_local_fused<LAYOUT_YPAIR2>, ph.ypair, cls ? ys : 0L, true, route, ph.ypairR);
         } else {
-            launch(k_local_fused<LAYOUT_FT, false, 1, false, false>, route, true);
+            launch(k_local_fused<LAYOUT_FT, false, 1, false, false>, ph.vol, vs, true, route, 0);
         }
     } else {
-        launch(kern, nullptr, nobox);
+        launch(kern, ph.vol, vs, nobox, nullptr, 0);
     }
     THX_LAUNCH_CHECK();
-    if (evEnd) THX_HIP(hipEventRecord(evEnd, s));
+    if (ph.evEnd) THX_HIP(hipEventRecord(ph.evEnd, s));
     if (fuse) return THX_OK;
-    return launch_local_weights(d, nR, nT, pC, pR, pT, wC, wR, wT, baseL, nImg, s, act, nAct);
+    return nD ? launch_local_weights_d(d, nR, nT, nD, ph.pC, ph.pR, ph.pT, ph.pD, ph.wC, ph.wR, ph.wT,
+                                       ph.wD, ph.baseL, nImg, s, act, nAct)
+              : launch_local_weights(d, nR, nT, ph.pC, ph.pR, ph.pT, ph.wC, ph.wR, ph.wT, ph.baseL,
+                                     nImg, s, act, nAct);
 }
 using thx::local_phase_impl;
 
-extern "C" int thx_local_phase(const float* vol, int volLayout, int vdim, int pf,
-                               const double* quat, int nR, const double* trans,
-                               int nT, const double* pC, const double* pR,
-                               const double* pT, const float* dat,
-                               const float* ctf, const float* sigRcp,
-                               const int* iCol, const int* iRow, const int* pxOrder,
-                               int nOrd, int nPxl, int idim, int nImg, float* wC, float* wR,
-                               float* wT, float* baseL, float* dvp,
-                               void* workspace, size_t wsBytes,
-                               thx_stream_t stream)
+// The arguments every entry point shares, in the order the C ABI lists them.
+static thx::LocalPhase phase_args(const thx_local_sel* sel, const float* vol, int volLayout, int vdim,
+                                  int pf, const double* quat, int nR, const double* trans, int nT,
+                                  const double* pC, const double* pR, const double* pT,
+                                  const float* dat, const float* ctf, const float* sigRcp,
+                                  const int* iCol, const int* iRow, const int* pxOrder, int nOrd,
+                                  int nPxl, int idim, int nImg, float* wC, float* wR, float* wT,
+                                  float* baseL, float* dvp, void* workspace, size_t wsBytes,
+                                  thx_stream_t stream)
 {
-    return local_phase_impl(nullptr, nullptr, nullptr, vol, volLayout, vdim, pf, quat, nR, trans,
-                            nT, pC, pR, pT,
-                            dat, ctf, sigRcp, iCol, iRow, pxOrder, nOrd, nPxl, idim, nImg, wC, wR,
-                            wT, baseL, dvp, workspace, wsBytes, stream);
+    thx::LocalPhase ph;
+    ph.sel = sel; ph.vol = vol; ph.volLayout = volLayout; ph.vdim = vdim; ph.pf = pf;
+    ph.quat = quat; ph.nR = nR; ph.trans = trans; ph.nT = nT; ph.pC = pC; ph.pR = pR; ph.pT = pT;
+    ph.dat = dat; ph.ctf = ctf; ph.sigRcp = sigRcp; ph.nPxl = nPxl; ph.idim = idim; ph.nImg = nImg;
+    ph.iCol = iCol; ph.iRow = iRow; ph.pxOrder = pxOrder; ph.nOrd = nOrd;
+    ph.wC = wC; ph.wR = wR; ph.wT = wT; ph.baseL = baseL; ph.dvp = dvp;
+    ph.workspace = workspace; ph.wsBytes = wsBytes; ph.stream = stream;
+    return ph;
+}
+
+extern "C" int thx_local_phase(const float* vol, int volLayout, int vdim, int pf, const double* quat,
+                               int nR, const double* trans, int nT, const double* pC,
+                               const double* pR, const double* pT, const float* dat, const float* ctf,
+                               const float* sigRcp, const int* iCol, const int* iRow,
+                               const int* pxOrder, int nOrd, int nPxl, int idim, int nImg, float* wC,
+                               float* wR, float* wT, float* baseL, float* dvp, void* workspace,
+                               size_t wsBytes, thx_stream_t stream)
+{
+    return local_phase_impl(phase_args(nullptr, vol, volLayout, vdim, pf, quat, nR, trans, nT, pC, pR,
+                                       pT, dat, ctf, sigRcp, iCol, iRow, pxOrder, nOrd, nPxl, idim,
+                                       nImg, wC, wR, wT, baseL, dvp, workspace, wsBytes, stream));
 }
 
 extern "C" int thx_local_phase_sel(const thx_local_sel* sel, const float* vol, int volLayout,
@@ -1893,9 +1890,9 @@ extern "C" int thx_local_phase_sel(const thx_local_sel* sel, const float* vol, i
                                    float* baseL, float* dvp, void* workspace, size_t wsBytes,
                                    thx_stream_t stream)
 {
-    return local_phase_impl(sel, nullptr, nullptr, vol, volLayout, vdim, pf, quat, nR, trans, nT,
-                            pC, pR, pT, dat, ctf, sigRcp, iCol, iRow, pxOrder, nOrd, nPxl, idim,
-                            nImg, wC, wR, wT, baseL, dvp, workspace, wsBytes, stream);
+    return local_phase_impl(phase_args(sel, vol, volLayout, vdim, pf, quat, nR, trans, nT, pC, pR, pT,
+                                       dat, ctf, sigRcp, iCol, iRow, pxOrder, nOrd, nPxl, idim, nImg,
+                                       wC, wR, wT, baseL, dvp, workspace, wsBytes, stream));
 }
 
 extern "C" int thx_local_phase_d(const thx_local_sel* sel, const float* vol, int volLayout,
@@ -1909,9 +1906,11 @@ extern "C" int thx_local_phase_d(const thx_local_sel* sel, const float* vol, int
                                  size_t wsBytes, thx_stream_t stream)
 {
     THX_CHECK_ARG(nD > 0, "thx_local_phase_d: nD must be positive");
-    return local_phase_impl(sel, nullptr, nullptr, vol, volLayout, vdim, pf, quat, nR, trans, nT,
-                            pC, pR, pT, dat, ctfD, sigRcp, iCol, iRow, pxOrder, nOrd, nPxl, idim,
-                            nImg, wC, wR, wT, baseL, dvp, workspace, wsBytes, stream, nD, pD, wD);
+    thx::LocalPhase ph = phase_args(sel, vol, volLayout, vdim, pf, quat, nR, trans, nT, pC, pR, pT,
+                                    dat, ctfD, sigRcp, iCol, iRow, pxOrder, nOrd, nPxl, idim, nImg,
+                                    wC, wR, wT, baseL, dvp, workspace, wsBytes, stream);
+    ph.nD = nD; ph.pD = pD; ph.wD = wD;
+    return local_phase_impl(ph);
 }
 
 extern "C" int thx_local_phase_routed(const thx_local_sel* sel, const float* vol,
@@ -1925,10 +1924,11 @@ extern "C" int thx_local_phase_routed(const thx_local_sel* sel, const float* vol
                                       size_t wsBytes, thx_stream_t stream)
 {
     THX_CHECK_ARG(pxOrder, "thx_local_phase_routed: needs pxOrder (thx_pixel_tile_order)");
-    return local_phase_impl(sel, nullptr, nullptr, vol, LAYOUT_FT, vdim, pf, quat, nR, trans, nT,
-                            pC, pR, pT, dat, ctf, sigRcp, iCol, iRow, pxOrder, nOrd, nPxl, idim,
-                            nImg, wC, wR, wT, baseL, dvp, workspace, wsBytes, stream, 0, nullptr,
-                            nullptr, ypair, route);
+    thx::LocalPhase ph = phase_args(sel, vol, LAYOUT_FT, vdim, pf, quat, nR, trans, nT, pC, pR, pT,
+                                    dat, ctf, sigRcp, iCol, iRow, pxOrder, nOrd, nPxl, idim, nImg,
+                                    wC, wR, wT, baseL, dvp, workspace, wsBytes, stream);
+    ph.ypair = ypair; ph.routeOut = route;
+    return local_phase_impl(ph);
 }
 
 // max iCol^2 + iRow^2 over the pixel set (one workgroup)
@@ -1988,10 +1988,11 @@ extern "C" int thx_local_phase_routed_ball(const thx_local_sel* sel, const float
     THX_CHECK_ARG(pf * std::sqrt((double)r2) + 2 <= ballR,
                   "thx_local_phase_routed_ball: the pixel ring (pf r_max = %g) needs ballR >= %d",
                   pf * std::sqrt((double)r2), (int)std::ceil(pf * std::sqrt((double)r2)) + 2);
-    return local_phase_impl(sel, nullptr, nullptr, vol, LAYOUT_FT, vdim, pf, quat, nR, trans, nT,
-                            pC, pR, pT, dat, ctf, sigRcp, iCol, iRow, pxOrder, nOrd, nPxl, idim,
-                            nImg, wC, wR, wT, baseL, dvp, workspace, wsBytes, stream, 0, nullptr,
-                            nullptr, ball, route, nullptr, ballR);
+    thx::LocalPhase ph = phase_args(sel, vol, LAYOUT_FT, vdim, pf, quat, nR, trans, nT, pC, pR, pT,
+                                    dat, ctf, sigRcp, iCol, iRow, pxOrder, nOrd, nPxl, idim, nImg,
+                                    wC, wR, wT, baseL, dvp, workspace, wsBytes, stream);
+    ph.ypair = ball; ph.ypairR = ballR; ph.routeOut = route;
+    return local_phase_impl(ph);
 }
 
 namespace thx {
@@ -2015,7 +2016,6 @@ bool step_plan_build(const int* pxOrder, int nOrd, const float* dat, const float
 // no CTF search, 64 KiB boxes) -- the phases that can use a y-pair copy
 bool phase_routed(int volLayout, int pf, int nPxl, int nD)
 {
-    return volLayout == LAYOUT_FT && !nD &&
-           !(pf * std::sqrt(2.0 * nPxl / M_PI) >= BIGBOX_MIN_R);
+    return volLayout == LAYOUT_FT && !nD && !big_box(pf, nPxl);
 }
 }  // namespace thx

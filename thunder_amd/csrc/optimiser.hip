@@ -2387,10 +2387,21 @@ struct Expect : ExpectArgs {
     // the mean without a copy); the caller's buffers get the last one
     double *cq = quat, *ct = trans, *nq = p.tmpQ, *nt = p.tmpT;
     bool meanAhead = false;     // the next phase's perturbation mean, already running on its lane
+    // what every 3D phase of the call shares (likelihood() adds the rest): the
+    // caller's cell copy or vol with the y-pair copy for the device route
+    thx::LocalPhase phase3d;
 
     Expect(const ExpectArgs& a, const Plan& pl, SideStream& side)
         : ExpectArgs(a), c(*a.cfg), p(pl), vari(side.vari), mean(side.mean)
     {
+        thx::LocalPhase& ph = phase3d;
+        ph.vol = c.volCells ? c.volCells : vol; ph.volLayout = c.volCells ? 1 : 0;
+        ph.vdim = c.vdim; ph.pf = c.pf; ph.ypair = p.ypair; ph.nR = c.mLR; ph.nT = c.mLT; ph.nD = mLD;
+        ph.pC = p.pC; ph.pR = pR; ph.pT = pT; ph.pD = cs ? cs->pD : nullptr;
+        ph.dat = dat; ph.sigRcp = sigRcp; ph.nPxl = nPxl; ph.idim = c.idim; ph.nImg = nImg;
+        ph.iCol = iCol; ph.iRow = iRow; ph.pxOrder = pxOrder; ph.nOrd = nOrd; ph.sel = &sel;
+        ph.wC = p.wC; ph.wR = p.wR; ph.wT = p.wT; ph.wD = p.wD; ph.baseL = p.base;
+        ph.workspace = p.localWs; ph.wsBytes = p.localWsBytes; ph.stream = stream;
     }
     // every exit, error paths included, leaves no work on a lane behind s
     ~Expect()
@@ -2604,17 +2615,12 @@ struct Expect : ExpectArgs {
             if (ev) THX_HIP(hipEventRecord(ev[2 * pi + 1], s));
             return THX_OK;
         }
-        // the phases' volume: the caller's cell copy or vol (with the y-pair copy
-        // for the device route)
-        return thx::local_phase_impl(&sel, ev ? ev[2 * pi] : nullptr, ev ? ev[2 * pi + 1] : nullptr,
-                                     c.volCells ? c.volCells : vol, c.volCells ? 1 : 0, c.vdim,
-                                     c.pf, cq, c.mLR, ct, c.mLT, p.pC, pR, pT,
-                                     dat, cs ? p.ctfD : ctf, sigRcp, iCol, iRow, pxOrder, nOrd,
-                                     nPxl, c.idim, nImg, p.wC, p.wR, p.wT, p.base, nullptr,
-                                     p.localWs, p.localWsBytes, stream, mLD,
-                                     cs ? cs->pD : nullptr, p.wD, p.ypair,
-                                     pi < c.nPhaseRoute ? c.phaseRoute + pi : nullptr, routeSample,
-                                     ypairR, planned ? stepPlan : nullptr);
+        thx::LocalPhase ph = phase3d;       // + what this phase adds
+        ph.quat = cq; ph.trans = ct; ph.ctf = cs ? p.ctfD : ctf; ph.ypairR = ypairR;
+        ph.evBeg = ev ? ev[2 * pi] : nullptr; ph.evEnd = ev ? ev[2 * pi + 1] : nullptr;
+        ph.routeOut = pi < c.nPhaseRoute ? c.phaseRoute + pi : nullptr;
+        ph.routeSample = routeSample; ph.stepPlan = planned ? stepPlan : nullptr;
+        return thx::local_phase_impl(ph);
     }
 
     // resample R and T (and D) by the phase marginals; ancestors gathered into

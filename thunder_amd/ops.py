@@ -384,6 +384,18 @@ def volume_ypair_ball(vol, R):
     return out
 
 
+def _phase_cloud(quat, trans, pC, pR, pT, nImg, dev):
+    """Checks a phase's cloud and priors; returns nR, nT and empty wC, wR, wT, baseL."""
+    nR, nT = quat.shape[1], trans.shape[1]
+    _req(quat, torch.float64, (nImg, nR, 4), "quat")
+    _req(trans, torch.float64, (nImg, nT, 2), "trans")
+    _req(pC, torch.float64, (nImg,), "pC")
+    _req(pR, torch.float64, (nImg, nR), "pR")
+    _req(pT, torch.float64, (nImg, nT), "pT")
+    return (nR, nT) + tuple(torch.empty(nImg, *sh, dtype=torch.float32, device=dev)
+                            for sh in ((), (nR,), (nT,), ()))
+
+
 def local_phase(vol, quat, trans, pC, pR, pT, dat, ctf_, sig, px, want_dvp=False, cells=None,
                 tiled=True, ypair=None, routed=False, ball=None, ball_r=0):
     """cells / ypair: optional thx_volume_cells / thx_volume_ypair copy of vol.
@@ -404,58 +416,30 @@ def local_phase(vol, quat, trans, pC, pR, pT, dat, ctf_, sig, px, want_dvp=False
     nImg, nPxl = _images(dat, ctf_, sig)
     if nPxl != px.n:
         raise ValueError("pixel set / image size mismatch")
-    nR, nT = quat.shape[1], trans.shape[1]
     dev = dat.device
-    _req(quat, torch.float64, (nImg, nR, 4), "quat")
-    _req(trans, torch.float64, (nImg, nT, 2), "trans")
-    _req(pC, torch.float64, (nImg,), "pC")
-    _req(pR, torch.float64, (nImg, nR), "pR")
-    _req(pT, torch.float64, (nImg, nT), "pT")
+    nR, nT, wC, wR, wT, base = _phase_cloud(quat, trans, pC, pR, pT, nImg, dev)
     if routed and ypair is not None:
         _req(ypair, torch.complex64, _ypair_shape(vol), "ypair")
-    wC = torch.empty(nImg, dtype=torch.float32, device=dev)
-    wR = torch.empty(nImg, nR, dtype=torch.float32, device=dev)
-    wT = torch.empty(nImg, nT, dtype=torch.float32, device=dev)
-    base = torch.empty(nImg, dtype=torch.float32, device=dev)
     d = torch.empty(nImg, nR, nT, dtype=torch.float32, device=dev) if want_dvp else None
     route = torch.full((1,), -2, dtype=torch.int32, device=dev)
     ws = workspace(lib().thx_local_phase_workspace(min(nImg, 65535), nR, nT,
                                                    len(px.order) if tiled else nPxl), dev)
+    # the entry point and what it takes before / after the shared arguments
+    if ball is not None:
+        fn, lead = "thx_local_phase_routed_ball", (None, _ptr(vol), _ptr(ball), ball_r)
+        tail = (_ptr(route),)
+    elif routed:
+        fn, lead, tail = "thx_local_phase_routed", (None, _ptr(vol), _ptr(ypair)), (_ptr(route),)
+    else:
+        fn, lead, tail = "thx_local_phase", (_ptr(src), layout), ()
     for l0 in range(0, nImg, 65535):
         nb = min(65535, nImg - l0)
-        if routed and ball is not None:
-            check(lib().thx_local_phase_routed_ball(None, _ptr(vol), _ptr(ball), ball_r, vdim, px.pf,
-                                                    _ptr(quat[l0:]), nR, _ptr(trans[l0:]), nT,
-                                                    _ptr(pC[l0:]), _ptr(pR[l0:]), _ptr(pT[l0:]),
-                                                    _ptr(dat[l0:]), _ptr(ctf_[l0:]), _ptr(sig[l0:]),
-                                                    _ptr(px.d_iCol), _ptr(px.d_iRow), _ptr(px.d_order),
-                                                    len(px.order), nPxl, px.idim, nb, _ptr(wC[l0:]),
-                                                    _ptr(wR[l0:]), _ptr(wT[l0:]), _ptr(base[l0:]),
-                                                    _ptr(d[l0:]) if d is not None else None, _ptr(route),
-                                                    _ptr(ws), ws.numel(), _stream(dev)),
-                  "thx_local_phase_routed_ball")
-            continue
-        if routed:
-            check(lib().thx_local_phase_routed(None, _ptr(vol), _ptr(ypair) if ypair is not None else None,
-                                               vdim, px.pf, _ptr(quat[l0:]), nR, _ptr(trans[l0:]), nT,
-                                               _ptr(pC[l0:]), _ptr(pR[l0:]), _ptr(pT[l0:]),
-                                               _ptr(dat[l0:]), _ptr(ctf_[l0:]), _ptr(sig[l0:]),
-                                               _ptr(px.d_iCol), _ptr(px.d_iRow), _ptr(px.d_order),
-                                               len(px.order), nPxl, px.idim, nb, _ptr(wC[l0:]),
-                                               _ptr(wR[l0:]), _ptr(wT[l0:]), _ptr(base[l0:]),
-                                               _ptr(d[l0:]) if d is not None else None, _ptr(route),
-                                               _ptr(ws), ws.numel(), _stream(dev)),
-                  "thx_local_phase_routed")
-            continue
-        check(lib().thx_local_phase(_ptr(src), layout, vdim, px.pf, _ptr(quat[l0:]), nR,
-                                    _ptr(trans[l0:]),
-                                    nT, _ptr(pC[l0:]), _ptr(pR[l0:]), _ptr(pT[l0:]), _ptr(dat[l0:]),
-                                    _ptr(ctf_[l0:]), _ptr(sig[l0:]), _ptr(px.d_iCol),
-                                    _ptr(px.d_iRow), _ptr(px.d_order) if tiled else None,
-                                    len(px.order), nPxl, px.idim, nb, _ptr(wC[l0:]),
-                                    _ptr(wR[l0:]), _ptr(wT[l0:]), _ptr(base[l0:]),
-                                    _ptr(d[l0:]) if d is not None else None, _ptr(ws),
-                                    ws.numel(), _stream(dev)), "thx_local_phase")
+        check(getattr(lib(), fn)(
+            *lead, vdim, px.pf, _ptr(quat[l0:]), nR, _ptr(trans[l0:]), nT, _ptr(pC[l0:]), _ptr(pR[l0:]),
+            _ptr(pT[l0:]), _ptr(dat[l0:]), _ptr(ctf_[l0:]), _ptr(sig[l0:]), _ptr(px.d_iCol),
+            _ptr(px.d_iRow), _ptr(px.d_order) if tiled else None, len(px.order), nPxl, px.idim, nb,
+            _ptr(wC[l0:]), _ptr(wR[l0:]), _ptr(wT[l0:]), _ptr(base[l0:]),
+            _ptr(d[l0:]) if d is not None else None, *tail, _ptr(ws), ws.numel(), _stream(dev)), fn)
     if routed:
         return wC, wR, wT, base, d, int(route.item())
     return wC, wR, wT, base, d
@@ -468,26 +452,17 @@ def local_phase_d(vol, quat, trans, pC, pR, pT, pD, dat, ctfD, sig, px, want_dvp
     vdim = _vol_dim(vol)
     layout, src = _layout(vol, cells)
     nImg, nPxl = dat.shape
-    nR, nT, nD = quat.shape[1], trans.shape[1], pD.shape[1]
-    dev = dat.device
+    nD, dev = pD.shape[1], dat.device
     _req(dat, torch.complex64, (nImg, nPxl), "dat")
     _req(ctfD, torch.float32, (nImg, nD, nPxl), "ctfD")
     _req(sig, torch.float32, (nImg, nPxl), "sig")
     if nPxl != px.n:
         raise ValueError("pixel set / image size mismatch")
-    _req(quat, torch.float64, (nImg, nR, 4), "quat")
-    _req(trans, torch.float64, (nImg, nT, 2), "trans")
-    _req(pC, torch.float64, (nImg,), "pC")
-    _req(pR, torch.float64, (nImg, nR), "pR")
-    _req(pT, torch.float64, (nImg, nT), "pT")
+    nR, nT, wC, wR, wT, base = _phase_cloud(quat, trans, pC, pR, pT, nImg, dev)
     _req(pD, torch.float64, (nImg, nD), "pD")
     if nImg > 65535:
         raise ValueError("local_phase_d: at most 65535 images per call")
-    wC = torch.empty(nImg, dtype=torch.float32, device=dev)
-    wR = torch.empty(nImg, nR, dtype=torch.float32, device=dev)
-    wT = torch.empty(nImg, nT, dtype=torch.float32, device=dev)
     wD = torch.empty(nImg, nD, dtype=torch.float32, device=dev)
-    base = torch.empty(nImg, dtype=torch.float32, device=dev)
     d = torch.empty(nImg, nR, nT, nD, dtype=torch.float32, device=dev) if want_dvp else None
     ws = workspace(lib().thx_local_phase_workspace(nImg, nR, nT * nD,
                                                    len(px.order) if tiled else nPxl), dev)
