@@ -464,8 +464,8 @@ def test_calvari_replayed_second_fixed_point():
     (calvari_acg_impl), with the second pass's own stopping rule.  Against
     the oracle's two passes at 1e-6, on clouds where the oracle's second
     pass stops before, at and after its first (asserted: all three occur),
-    resampled clouds of few ancestors and 200-particle clouds (the strided
-    path)."""
+    resampled clouds of few ancestors, 200-particle clouds (the strided path)
+    and clouds of 128 and 129 (the register path full, and one past it)."""
     from oracle import particle as op
     rng = np.random.default_rng(29)
     clouds = []
@@ -482,6 +482,13 @@ def test_calvari_replayed_second_fixed_point():
         q[:, 1] *= 0.2
         special.append(q / np.linalg.norm(q, axis=1, keepdims=True))
     clouds.append(np.stack(special))
+    # the register path exactly full (128 particles) and the strided path just
+    # past it, from a generator of their own: the clouds above keep their draws
+    rng_edge = np.random.default_rng(31)
+    for m in (128, 129):
+        for spread in (1.0, 3.0, 10.0, 30.0, 60.0):
+            clouds.append(synth.clustered_quaternions(6, m, spread, rng_edge))
+        clouds.append(np.stack([_runs_cloud(rng_edge, 12, m, 3.0) for _ in range(6)]))
     before = after = same = 0
     for quat in clouds:
         nImg, m = quat.shape[:2]

@@ -159,6 +159,17 @@ THX_DEV float wave_max(float v)
     return v;
 }
 
+namespace thx {
+// Memory hand-off between the lanes of one wave: what any lane stored (global
+// or LDS) before it, every lane of the wave reads after it.
+THX_DEV void wave_mem_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+}  // namespace thx
+
 // Trilinear Fourier-space gather of Volume::getByInterpolationFT
 // (src/Image/Volume.cpp:314-338): Hermitian fold when x < 0 (conjHalf,
 // include/Image/Volume.h:135-147), floor + 8 weights

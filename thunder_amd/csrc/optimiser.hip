@@ -100,37 +100,7 @@ THX_DEV double rcp_nr(double x)
     return fma(r, fma(-x, r, 1.0), r);
 }
 
-THX_DEV double inv4(const double* m, double* o)
-{
-    const double s0 = m[0] * m[5] - m[4] * m[1], s1 = m[0] * m[6] - m[4] * m[2];
-    const double s2 = m[0] * m[7] - m[4] * m[3], s3 = m[1] * m[6] - m[5] * m[2];
-    const double s4 = m[1] * m[7] - m[5] * m[3], s5 = m[2] * m[7] - m[6] * m[3];
-    const double c5 = m[10] * m[15] - m[14] * m[11], c4 = m[9] * m[15] - m[13] * m[11];
-    const double c3 = m[9] * m[14] - m[13] * m[10], c2 = m[8] * m[15] - m[12] * m[11];
-    const double c1 = m[8] * m[14] - m[12] * m[10], c0 = m[8] * m[13] - m[12] * m[9];
-    const double det = s0 * c5 - s1 * c4 + s2 * c3 + s3 * c2 - s4 * c1 + s5 * c0;
-    const double r = det != 0.0 ? rcp_nr(det) : __builtin_nan("");
-    o[0] = (m[5] * c5 - m[6] * c4 + m[7] * c3) * r;
-    o[1] = (-m[1] * c5 + m[2] * c4 - m[3] * c3) * r;
-    o[2] = (m[13] * s5 - m[14] * s4 + m[15] * s3) * r;
-    o[3] = (-m[9] * s5 + m[10] * s4 - m[11] * s3) * r;
-    o[5] = (m[0] * c5 - m[2] * c2 + m[3] * c1) * r;
-    o[6] = (-m[12] * s5 + m[14] * s2 - m[15] * s1) * r;
-    o[7] = (m[8] * s5 - m[10] * s2 + m[11] * s1) * r;
-    o[10] = (m[12] * s4 - m[13] * s2 + m[15] * s0) * r;
-    o[11] = (-m[8] * s4 + m[9] * s2 - m[11] * s0) * r;
-    o[15] = (m[8] * s3 - m[9] * s1 + m[10] * s0) * r;
-    o[4] = o[1]; o[8] = o[2]; o[12] = o[3];
-    o[9] = o[6]; o[13] = o[7]; o[14] = o[11];
-    return det;
-}
-
-// inv4 with every 2x2 minor compensated (Kahan's a d - b c: the product b c
-// and its FMA residual): the minors of a near-rank-1 A cancel by about the
-// ratio of its eigenvalues, and the plain products leave the small
-// eigen-directions of A^-1 -- the ones a de-meaning rotation exposes --
-// with ~1e-6 relative error on a cloud of 1e-4 spread, the compensated ones
-// with ~1e-8.  Used by calvari_acg_impl, whose second fixed point reads them.
+// a d - b c compensated (Kahan: the product b c and its FMA residual)
 THX_DEV double dop2(double a, double d, double b, double c)
 {
     const double w = b * c;
@@ -138,14 +108,24 @@ THX_DEV double dop2(double a, double d, double b, double c)
     return fma(a, d, -w) + e;
 }
 
-THX_DEV double inv4_acc(const double* m, double* o)
+// ACC: every 2x2 minor compensated (dop2).  The minors of a near-rank-1 A
+// cancel by about the ratio of its eigenvalues, and the plain products leave
+// the small eigen-directions of A^-1 -- the ones a de-meaning rotation
+// exposes -- with ~1e-6 relative error on a cloud of 1e-4 spread, the
+// compensated ones with ~1e-8.  Used by calvari_acg_impl, whose second fixed
+// point reads them.
+template <bool ACC>
+THX_DEV double inv4(const double* m, double* o)
 {
-    const double s0 = dop2(m[0], m[5], m[4], m[1]), s1 = dop2(m[0], m[6], m[4], m[2]);
-    const double s2 = dop2(m[0], m[7], m[4], m[3]), s3 = dop2(m[1], m[6], m[5], m[2]);
-    const double s4 = dop2(m[1], m[7], m[5], m[3]), s5 = dop2(m[2], m[7], m[6], m[3]);
-    const double c5 = dop2(m[10], m[15], m[14], m[11]), c4 = dop2(m[9], m[15], m[13], m[11]);
-    const double c3 = dop2(m[9], m[14], m[13], m[10]), c2 = dop2(m[8], m[15], m[12], m[11]);
-    const double c1 = dop2(m[8], m[14], m[12], m[10]), c0 = dop2(m[8], m[13], m[12], m[9]);
+    auto mnr = [](double a, double d, double b, double c) {
+        return ACC ? dop2(a, d, b, c) : a * d - b * c;
+    };
+    const double s0 = mnr(m[0], m[5], m[4], m[1]), s1 = mnr(m[0], m[6], m[4], m[2]);
+    const double s2 = mnr(m[0], m[7], m[4], m[3]), s3 = mnr(m[1], m[6], m[5], m[2]);
+    const double s4 = mnr(m[1], m[7], m[5], m[3]), s5 = mnr(m[2], m[7], m[6], m[3]);
+    const double c5 = mnr(m[10], m[15], m[14], m[11]), c4 = mnr(m[9], m[15], m[13], m[11]);
+    const double c3 = mnr(m[9], m[14], m[13], m[10]), c2 = mnr(m[8], m[15], m[12], m[11]);
+    const double c1 = mnr(m[8], m[14], m[12], m[10]), c0 = mnr(m[8], m[13], m[12], m[9]);
     const double det = s0 * c5 - s1 * c4 + s2 * c3 + s3 * c2 - s4 * c1 + s5 * c0;
     const double r = det != 0.0 ? rcp_nr(det) : __builtin_nan("");
     o[0] = (m[5] * c5 - m[6] * c4 + m[7] * c3) * r;
@@ -161,6 +141,24 @@ THX_DEV double inv4_acc(const double* m, double* o)
     o[4] = o[1]; o[8] = o[2]; o[12] = o[3];
     o[9] = o[6]; o[13] = o[7]; o[14] = o[11];
     return det;
+}
+
+// The identity, and a symmetric 4x4 from / to its upper triangle (row-major j <= k)
+THX_DEV void sym4_identity(double* M)
+{
+    for (int k = 0; k < 16; k++) M[k] = (k % 5 == 0) ? 1.0 : 0.0;
+}
+THX_DEV void sym4_from10(const double* u, double* M)
+{
+    int t = 0;
+    for (int j = 0; j < 4; j++)
+        for (int k = j; k < 4; k++, t++) M[4 * j + k] = M[4 * k + j] = u[t];
+}
+THX_DEV void sym4_to10(const double* M, double* u)
+{
+    int t = 0;
+    for (int j = 0; j < 4; j++)
+        for (int k = j; k < 4; k++, t++) u[t] = M[4 * j + k];
 }
 
 // A symmetric matrix packed as its upper triangle with the off-diagonal
@@ -222,30 +220,39 @@ THX_DEV double group_sum(double v)
 // inferACG(dmat44&, const dmat4&), DirectionalStat.cpp:93-145: Tyler's fixed
 // point B = 4/nf sum q q^T / (q^T A^-1 q) from B = I while sum|A - B| > 1e-3
 // (a NaN criterion ends the loop, as in the reference's `while`); returns the
-// last A.  Particle q_i is read as pre q_i (pre = conj(mean) de-means).
-// Clouds of up to GROUP * QREG particles keep this lane's (de-meaned)
-// particles in registers across the iterations -- the loop is a serial
-// chain, and re-reading them from L2 every iteration was its latency.  Each
-// lane then holds a block of QREG consecutive particles as runs of equal
-// ones: a resampled cloud stores an ancestor's copies next to each other, so
-// the term of a run is taken once with its multiplicity.  The degenerate
-// clouds that run the fixed point to its cap are the ones with a few
-// ancestors, so their iterations cost one or two terms per lane instead of
-// QREG.  The sum is the reference's up to rounding (multiplicity x term for
-// repeated additions, block for strided order).
+// last A.
+// Clouds of up to GROUP * QREG particles keep this lane's particles in
+// registers across the iterations -- the loop is a serial chain, and
+// re-reading them from L2 every iteration was its latency.  Each lane then
+// holds a block of QREG consecutive particles as runs of equal ones: a
+// resampled cloud stores an ancestor's copies next to each other, so the term
+// of a run is taken once with its multiplicity.  The degenerate clouds that
+// run the fixed point to its cap are the ones with a few ancestors, so their
+// iterations cost one or two terms per lane instead of QREG.  The sum is the
+// reference's up to rounding (multiplicity x term for repeated additions,
+// block for strided order).
 constexpr int QREG = 128 / GROUP;
 
+// The cloud of one image as the fixed point reads it: REG -- this lane's
+// block as runs in registers (load() first), else strided from Q.
 // idx (optional): particle i is Q[idx[i]] -- a resampled cloud read through
 // its ancestors, in the gathered order, without the gather
 template <bool REG>
-THX_DEV int infer_acg_impl(const double* Q, int m, const double* pre, int lane, double* A,
-                           int maxIt, const int* idx = nullptr)
-{
-    auto at = [&](int i) { return Q + 4 * (idx ? idx[i] : i); };
-    double qr[REG ? QREG : 1][4];
-    int nd = 0, nIn = 0;                          // runs, particles this lane holds
+struct AcgCloud {
+    double qr[REG ? QREG : 1][4];                 // the heads of this lane's runs
     unsigned runs = 0;                            // bit p: block particle p starts a run
-    if (REG) {
+    int nd = 0, nIn = 0;                          // runs, particles this lane holds
+    const double* Q;
+    int m, lane;
+    const int* idx;
+
+    THX_DEV AcgCloud(const double* Q, int m, int lane, const int* idx)
+        : Q(Q), m(m), lane(lane), idx(idx) {}
+    THX_DEV const double* at(int i) const { return Q + 4 * (idx ? idx[i] : i); }
+
+    THX_DEV void load()
+    {
+        if (!REG) return;
         const int i0 = lane * QREG;
         nIn = max(0, min(QREG, m - i0));
         unsigned starts = 0;
@@ -267,17 +274,20 @@ THX_DEV int infer_acg_impl(const double* Q, int m, const double* pre, int lane, 
             if (starts) {
                 const double* c = at(i0 + __builtin_ctz(starts));
                 starts &= starts - 1;
-                if (pre) qmul(pre, c, qr[p]);
-                else for (int k = 0; k < 4; k++) qr[p][k] = c[k];
+                for (int k = 0; k < 4; k++) qr[p][k] = c[k];
             }
         }
     }
-    double B[16];
-    for (int k = 0; k < 16; k++) B[k] = (k % 5 == 0) ? 1.0 : 0.0;
-    for (int it = 0; it < maxIt; it++) {
+
+    // One pass of the fixed point: A <- B, B <- F(A); returns sum |A - B|.
+    // ACC: inv4's compensated minors.  fromMem: the particles re-read from Q
+    // although REG (the registers of the cloud are then dead).
+    template <bool ACC>
+    THX_DEV double step(double* A, double* B, bool fromMem) const
+    {
         for (int k = 0; k < 16; k++) A[k] = B[k];
         double Ai[16], Mp[10];
-        inv4(A, Ai);
+        inv4<ACC>(A, Ai);
         pack10(Ai, Mp);
         double b[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, nf = 0.0;
         auto term = [&](const double* q, double w) {
@@ -289,7 +299,7 @@ THX_DEV int infer_acg_impl(const double* Q, int m, const double* pre, int lane, 
             }
             nf += r;
         };
-        if (REG) {
+        if (REG && !fromMem) {
             unsigned rs = runs;
 #pragma unroll
             for (int p = 0; p < QREG; p++) {
@@ -300,31 +310,37 @@ THX_DEV int infer_acg_impl(const double* Q, int m, const double* pre, int lane, 
                 }
             }
         } else {
-            for (int i = lane; i < m; i += GROUP) {
-                double q[4];
-                const double* c = at(i);
-                if (pre) qmul(pre, c, q);
-                else for (int k = 0; k < 4; k++) q[k] = c[k];
-                term(q, 1.0);
-            }
+            for (int i = lane; i < m; i += GROUP) term(at(i), 1.0);
         }
         for (int t = 0; t < 10; t++) b[t] = group_sum(b[t]);
         nf = group_sum(nf);
-        int t = 0;
-        for (int j = 0; j < 4; j++)
-            for (int k = j; k < 4; k++, t++) B[4 * j + k] = B[4 * k + j] = b[t] * (4.0 * rcp_nr(nf));
+        for (int t = 0; t < 10; t++) b[t] = b[t] * (4.0 * rcp_nr(nf));
+        sym4_from10(b, B);
         double crit = 0.0;
         for (int k = 0; k < 16; k++) crit += fabs(A[k] - B[k]);
-        if (!(crit > 1e-3)) return it + 1;
+        return crit;
     }
+};
+
+// The fixed point from B = I, at most maxIt passes; A: the last A (every
+// lane); returns the passes made.
+template <bool REG>
+THX_DEV int infer_acg_impl(const double* Q, int m, int lane, double* A, int maxIt, const int* idx)
+{
+    AcgCloud<REG> cloud(Q, m, lane, idx);
+    cloud.load();
+    double B[16];
+    sym4_identity(B);
+    for (int it = 0; it < maxIt; it++)
+        if (!(cloud.template step<false>(A, B, false) > 1e-3)) return it + 1;
     return maxIt;
 }
 
-THX_DEV int infer_acg(const double* Q, int m, const double* pre, int lane, double* A,
-                      int maxIt = 256, const int* idx = nullptr)
+THX_DEV int infer_acg(const double* Q, int m, int lane, double* A, int maxIt = 256,
+                      const int* idx = nullptr)
 {
-    return m <= GROUP * QREG ? infer_acg_impl<true>(Q, m, pre, lane, A, maxIt, idx)
-                             : infer_acg_impl<false>(Q, m, pre, lane, A, maxIt, idx);
+    return m <= GROUP * QREG ? infer_acg_impl<true>(Q, m, lane, A, maxIt, idx)
+                             : infer_acg_impl<false>(Q, m, lane, A, maxIt, idx);
 }
 
 // Unit eigenvector of the largest eigenvalue of a symmetric 4x4 (cyclic
@@ -332,7 +348,8 @@ THX_DEV int infer_acg(const double* Q, int m, const double* pre, int lane, doubl
 THX_DEV void principal_axis(const double* A0, double* v)
 {
     double a[16], V[16];
-    for (int k = 0; k < 16; k++) { a[k] = A0[k]; V[k] = (k % 5 == 0) ? 1.0 : 0.0; }
+    for (int k = 0; k < 16; k++) a[k] = A0[k];
+    sym4_identity(V);
     for (int sweep = 0; sweep < 32; sweep++) {
         double off = 0.0, dia = 0.0;
         for (int p = 0; p < 4; p++)
@@ -371,8 +388,7 @@ THX_DEV void principal_axis(const double* A0, double* v)
     for (int k = 0; k < 4; k++) v[k] = V[4 * k + best] / n;
 }
 
-// calVari's two fixed points from one (k_pf_calvari with a history buffer).
-// The de-meaned cloud q' = c q (c = conj(mean), a unit quaternion) is the
+// calVari's two fixed points from one (k_pf_calvari).  The de-meaned cloud q' = c q (c = conj(mean), a unit quaternion) is the
 // cloud under the orthogonal map M: q -> c q, and Tyler's map commutes with
 // it (q'^T (M A M^T)^-1 q' = q^T A^-1 q, so F(M A M^T) = M F(A) M^T): from
 // B'_0 = I = M I M^T the second fixed point's iterates are B'_k = M B_k M^T,
@@ -390,11 +406,8 @@ constexpr int ACG_HIST = 10 * ACG_HIST_MAX;
 // B' = M B M^T of a symmetric B given as its upper triangle u (row-major j <= k)
 THX_DEV void acg_conj(const double* M, const double* u, double* P)
 {
-    double B[16];
-    int t = 0;
-    for (int j = 0; j < 4; j++)
-        for (int k = j; k < 4; k++, t++) B[4 * j + k] = B[4 * k + j] = u[t];
-    double T[16];
+    double B[16], T[16];
+    sym4_from10(u, B);
     for (int i = 0; i < 4; i++)
         for (int j = 0; j < 4; j++)
             T[4 * i + j] = M[4 * i] * B[j] + M[4 * i + 1] * B[4 + j] + M[4 * i + 2] * B[8 + j] +
@@ -421,81 +434,14 @@ THX_DEV void calvari_acg_impl(const double* Q, int m, int lane, double* __restri
                               double* A2)
 {
     constexpr int maxIt = ACG_HIST_MAX;
-    double qr[REG ? QREG : 1][4];
-    int nd = 0, nIn = 0;
-    unsigned runs = 0;
-    if (REG) {                                     // as infer_acg_impl
-        const int i0 = lane * QREG;
-        nIn = max(0, min(QREG, m - i0));
-        unsigned starts = 0;
-        double prev[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int p = 0; p < QREG; p++) {
-            if (p < nIn) {
-                const double* c = Q + 4 * (i0 + p);
-                const double c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];
-                if (p == 0 || c0 != prev[0] || c1 != prev[1] || c2 != prev[2] || c3 != prev[3])
-                    starts |= 1u << p;
-                prev[0] = c0; prev[1] = c1; prev[2] = c2; prev[3] = c3;
-            }
-        }
-        runs = starts;
-        nd = __builtin_popcount(starts);
-#pragma unroll
-        for (int p = 0; p < QREG; p++) {
-            if (starts) {
-                const double* c = Q + 4 * (i0 + __builtin_ctz(starts));
-                starts &= starts - 1;
-                for (int k = 0; k < 4; k++) qr[p][k] = c[k];
-            }
-        }
-    }
+    AcgCloud<REG> cloud(Q, m, lane, nullptr);
+    cloud.load();
     double A[16], B[16];
-    for (int k = 0; k < 16; k++) B[k] = (k % 5 == 0) ? 1.0 : 0.0;
-    // one pass of the fixed point (infer_acg_impl's): A <- B, B <- F(A); sum
-    // |A - B|.  fromMem: the particles re-read from Q (the continuation past
-    // the history, so that the register cloud is dead during the replay)
-    auto step = [&](bool fromMem) -> double {
-        for (int k = 0; k < 16; k++) A[k] = B[k];
-        double Ai[16], Mp[10];
-        inv4_acc(A, Ai);
-        pack10(Ai, Mp);
-        double b[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, nf = 0.0;
-        auto term = [&](const double* q, double w) {
-            const double r = w * rcp_nr(quad10(Mp, q));
-            int t = 0;
-            for (int j = 0; j < 4; j++) {
-                const double qj = q[j] * r;
-                for (int k = j; k < 4; k++) b[t++] += qj * q[k];
-            }
-            nf += r;
-        };
-        if (REG && !fromMem) {
-            unsigned rs = runs;
-#pragma unroll
-            for (int p = 0; p < QREG; p++) {
-                if (p < nd) {
-                    const int s0 = __builtin_ctz(rs);
-                    rs &= rs - 1;
-                    term(qr[p], (double)((rs ? __builtin_ctz(rs) : nIn) - s0));
-                }
-            }
-        } else {
-            for (int i = lane; i < m; i += GROUP) term(Q + 4 * i, 1.0);
-        }
-        for (int t = 0; t < 10; t++) b[t] = group_sum(b[t]);
-        nf = group_sum(nf);
-        int t = 0;
-        for (int j = 0; j < 4; j++)
-            for (int k = j; k < 4; k++, t++) B[4 * j + k] = B[4 * k + j] = b[t] * (4.0 * rcp_nr(nf));
-        double crit = 0.0;
-        for (int k = 0; k < 16; k++) crit += fabs(A[k] - B[k]);
-        return crit;
-    };
+    sym4_identity(B);
     // first fixed point, its iterates B_1 .. B_it1 kept
     int it1 = maxIt;
     for (int it = 0; it < maxIt; it++) {
-        const double crit = step(false);
+        const double crit = cloud.template step<true>(A, B, false);
         if (lane == 0) {
             double2* h2 = reinterpret_cast<double2*>(hist + 10 * it);
             h2[0] = make_double2(B[0], B[1]);
@@ -524,7 +470,7 @@ THX_DEV void calvari_acg_impl(const double* Q, int m, int lane, double* __restri
         bool stop = false;
         if (k < it1) {
             double Pk[16], Pn[16];
-            if (k == 0) for (int t = 0; t < 16; t++) Pk[t] = (t % 5 == 0) ? 1.0 : 0.0;
+            if (k == 0) sym4_identity(Pk);
             else acg_conj_hist(M, hist + 10 * (k - 1), Pk);
             acg_conj_hist(M, hist + 10 * k, Pn);
             double crit = 0.0;
@@ -535,7 +481,7 @@ THX_DEV void calvari_acg_impl(const double* Q, int m, int lane, double* __restri
         if (bits) kStop = k0 + __builtin_ctz(bits);
     }
     if (kStop == 0) {
-        for (int t = 0; t < 16; t++) A2[t] = (t % 5 == 0) ? 1.0 : 0.0;
+        sym4_identity(A2);
         return;
     }
     if (kStop > 0 || it1 == maxIt) {               // stopped in the history, or ran to the cap
@@ -543,28 +489,39 @@ THX_DEV void calvari_acg_impl(const double* Q, int m, int lane, double* __restri
         return;
     }
     // the second pass needs iterates past the first's: continue the first
-    // recurrence from (B_{it1 - 1}, B_it1)
-    double P[16];
-    {
-        double u[10];
-        int t = 0;
-        for (int j = 0; j < 4; j++)
-            for (int k = j; k < 4; k++, t++) u[t] = B[4 * j + k];
-        acg_conj(M, u, P);                         // B'_it1
-    }
+    // recurrence from (B_{it1 - 1}, B_it1), the particles re-read from Q so
+    // that the register cloud was dead during the replay
+    double P[16], u[10];
+    sym4_to10(B, u);
+    acg_conj(M, u, P);                             // B'_it1
     for (int k = it1; k < maxIt; k++) {
         for (int t = 0; t < 16; t++) A2[t] = P[t];
-        step(true);
-        double u[10], Pn[16];
-        int t = 0;
-        for (int j = 0; j < 4; j++)
-            for (int i = j; i < 4; i++, t++) u[t] = B[4 * j + i];
+        cloud.template step<true>(A, B, true);
+        double Pn[16];
+        sym4_to10(B, u);
         acg_conj(M, u, Pn);
         double crit = 0.0;
         for (int q = 0; q < 16; q++) crit += fabs(A2[q] - Pn[q]);
         if (!(crit > 1e-3)) return;
         for (int q = 0; q < 16; q++) P[q] = Pn[q];
     }
+}
+
+// Mean and sum of squared deviations from it (gsl_stats_mean, and what
+// gsl_stats_sd_m divides by n - 1) of each of the C interleaved components
+// of the n samples x[C i + c], over the GROUP lanes of an image: every lane
+// gets both.  The callers floor and divide, each in its own way.
+template <int C>
+THX_DEV void group_moments(const double* x, int n, int lane, double* mean, double* ss)
+{
+    for (int c = 0; c < C; c++) mean[c] = 0.0;
+    for (int i = lane; i < n; i += GROUP)
+        for (int c = 0; c < C; c++) mean[c] += x[C * i + c];
+    for (int c = 0; c < C; c++) mean[c] = group_sum(mean[c]) / n;
+    for (int c = 0; c < C; c++) ss[c] = 0.0;
+    for (int i = lane; i < n; i += GROUP)
+        for (int c = 0; c < C; c++) ss[c] += (x[C * i + c] - mean[c]) * (x[C * i + c] - mean[c]);
+    for (int c = 0; c < C; c++) ss[c] = group_sum(ss[c]);
 }
 
 // Particle::calVari (src/Particle.cpp:1004-1121), 3D: R -- de-mean by the
@@ -577,40 +534,23 @@ __global__ void __launch_bounds__(256) k_pf_calvari(int nImg, int mR, const doub
                                                     double kFloor, double sFloor,
                                                     double* __restrict__ kOut,
                                                     double* __restrict__ sOut,
-                                                    const int* __restrict__ done = nullptr,
-                                                    double* __restrict__ hist = nullptr)
+                                                    const int* __restrict__ done,
+                                                    double* __restrict__ hist)
 {
     const int l = (blockIdx.x * 256 + threadIdx.x) / GROUP;
     const int lane = threadIdx.x % GROUP;
     if (l >= nImg || (done && done[l])) return;
     const double* Q = quat + (size_t)l * mR * 4;
     double A[16];
-    if (hist) {
-        // both fixed points from one (calvari_acg_impl)
-        double* h = hist + (size_t)l * ACG_HIST;
-        if (mR <= GROUP * QREG) calvari_acg_impl<true>(Q, mR, lane, h, A);
-        else calvari_acg_impl<false>(Q, mR, lane, h, A);
-    } else {
-        double mean[4], cm[4];
-        infer_acg(Q, mR, nullptr, lane, A);
-        principal_axis(A, mean);
-        cm[0] = mean[0]; cm[1] = -mean[1]; cm[2] = -mean[2]; cm[3] = -mean[3];
-        infer_acg(Q, mR, cm, lane, A);
-    }
-    const double* Tr = trans + (size_t)l * mT * 2;
-    double sx = 0, sy = 0;
-    for (int i = lane; i < mT; i += GROUP) { sx += Tr[2 * i]; sy += Tr[2 * i + 1]; }
-    sx = group_sum(sx) / mT; sy = group_sum(sy) / mT;
-    double vx = 0, vy = 0;
-    for (int i = lane; i < mT; i += GROUP) {
-        vx += (Tr[2 * i] - sx) * (Tr[2 * i] - sx);
-        vy += (Tr[2 * i + 1] - sy) * (Tr[2 * i + 1] - sy);
-    }
-    vx = group_sum(vx); vy = group_sum(vy);
+    double* h = hist + (size_t)l * ACG_HIST;
+    if (mR <= GROUP * QREG) calvari_acg_impl<true>(Q, mR, lane, h, A);
+    else calvari_acg_impl<false>(Q, mR, lane, h, A);
+    double mu[2], ss[2];
+    group_moments<2>(trans + (size_t)l * mT * 2, mT, lane, mu, ss);
     if (lane == 0) {
         for (int j = 1; j < 4; j++) kOut[3 * l + j - 1] = fmax(kFloor, A[5 * j] / A[0]);
-        sOut[2 * l] = fmax(sFloor, mT > 1 ? sqrt(vx / (mT - 1)) : 0.0);
-        sOut[2 * l + 1] = fmax(sFloor, mT > 1 ? sqrt(vy / (mT - 1)) : 0.0);
+        sOut[2 * l] = fmax(sFloor, mT > 1 ? sqrt(ss[0] / (mT - 1)) : 0.0);
+        sOut[2 * l + 1] = fmax(sFloor, mT > 1 ? sqrt(ss[1] / (mT - 1)) : 0.0);
     }
 }
 
@@ -621,8 +561,8 @@ __global__ void __launch_bounds__(256) k_pf_calvari(int nImg, int mR, const doub
 THX_DEV void balance_rot(const double* Q, int m, int lane, double* w)
 {
     double A[16], Ai[16], Mp[10];
-    infer_acg(Q, m, nullptr, lane, A);
-    const double det = inv4(A, Ai);
+    infer_acg(Q, m, lane, A);
+    const double det = inv4<false>(A, Ai);
     pack10(Ai, Mp);
     const double sd = sqrt(det);
     double tot = 0.0;
@@ -896,9 +836,7 @@ __global__ void __launch_bounds__(256) k_pf_resample(int nImg, int nIn, int nOut
         int* k32 = reinterpret_cast<int*>(sKeyDyn + (size_t)(threadIdx.x >> 6) * regN);
         for (int i = lane; i < nIn; i += 64) k32[i] = pm[i];
         pm = k32;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        thx::wave_mem_sync();
     } else if (PRE && pm) {
         // (larger supports read the permutation where it lies)
     } else if (regSort) {
@@ -912,9 +850,7 @@ __global__ void __launch_bounds__(256) k_pf_resample(int nImg, int nIn, int nOut
         else if (REGKPL >= 2 && kpl == 2) shuffle_keys_reg<(REGKPL >= 2 ? 2 : 1)>(sh, nIn, lane, k32);
         else shuffle_keys_reg<1>(sh, nIn, lane, k32);
         pm = reinterpret_cast<int*>(k32);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        thx::wave_mem_sync();
     } else if (pm && nIn <= KMAX) {
         int ib = 0;
         while ((1 << ib) < nIn) ib++;
@@ -935,9 +871,7 @@ __global__ void __launch_bounds__(256) k_pf_resample(int nImg, int nIn, int nOut
         constexpr int PPL = 4;
         for (int k = 2; k <= N; k <<= 1)
             for (int j = k >> 1; j > 0; j >>= 1) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                thx::wave_mem_sync();
                 for (int p0 = 0; p0 < (N >> 1); p0 += 64 * PPL) {
                     uint64_t x[PPL], y[PPL];
 #pragma unroll
@@ -961,17 +895,13 @@ __global__ void __launch_bounds__(256) k_pf_resample(int nImg, int nIn, int nOut
         // row: every lane holds its (<= 32) indices in registers across the
         // barrier, so no word is overwritten before it has been read
         uint32_t idx[KMAX / 64];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        thx::wave_mem_sync();
 #pragma unroll
         for (int q = 0; q < KMAX / 64; q++) {
             const int i = lane + 64 * q;
             idx[q] = i < nIn ? (uint32_t)kk[i] : 0u;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        thx::wave_mem_sync();
         uint32_t* k32 = reinterpret_cast<uint32_t*>(kk);
 #pragma unroll
         for (int q = 0; q < KMAX / 64; q++) {
@@ -979,14 +909,10 @@ __global__ void __launch_bounds__(256) k_pf_resample(int nImg, int nIn, int nOut
             if (i < nIn) k32[i] = idx[q];
         }
         pm = reinterpret_cast<int*>(k32);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        thx::wave_mem_sync();
     } else if (pm) {
         for (int i = lane; i < nIn; i += 64) pm[i] = i;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        thx::wave_mem_sync();
         if (lane == 0) {
             Philox sh(seed, (uint32_t)l, stream, 0x5f1e);
             uint4 v = make_uint4(0, 0, 0, 0);
@@ -999,9 +925,7 @@ __global__ void __launch_bounds__(256) k_pf_resample(int nImg, int nIn, int nOut
                 pm[j] = a;
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        thx::wave_mem_sync();
     }
     auto at = [&](int i) { return pm ? pm[i] : i; };
     if (permOut)
@@ -1035,9 +959,7 @@ __global__ void __launch_bounds__(256) k_pf_resample(int nImg, int nIn, int nOut
         if (i < nIn) cdf[i] = carry + v;
         carry += __shfl(v, 63, 64);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    thx::wave_mem_sync();
     const double last = carry;
     Philox rng(seed, (uint32_t)l, stream, 0x5e5a);
     const double u0 = rng.uniform() / nOut;
@@ -1162,7 +1084,7 @@ __global__ void __launch_bounds__(256) k_pf_mean(int nImg, int mR, const double*
     const int lane = threadIdx.x % GROUP;
     if (l >= nImg || (done && done[l])) return;
     double A[16], mean[4];
-    const int it = infer_acg(quat + (size_t)l * mR * 4, mR, nullptr, lane, A, acgIters,
+    const int it = infer_acg(quat + (size_t)l * mR * 4, mR, lane, A, acgIters,
                              anc ? anc + (size_t)l * mR : nullptr);
     principal_axis(A, mean);
     if (lane == 0) {
@@ -1178,7 +1100,6 @@ __global__ void __launch_bounds__(256) k_pf_mean(int nImg, int mR, const double*
 THX_DEV void perturb_trans(double* Tr, double* pTl, int mT, double s0, double s1, double pf,
                            double transS, double transM, Philox& rng, int lane)
 {
-    double sx, sy, vx, vy;
     for (int i = lane; i < mT; i += GROUP) {
         const double2 g = rng.gauss2();
         double x = Tr[2 * i] + g.x * s0 * pf, y = Tr[2 * i + 1] + g.y * s1 * pf;
@@ -1188,23 +1109,14 @@ THX_DEV void perturb_trans(double* Tr, double* pTl, int mT, double s0, double s1
         }
         Tr[2 * i] = x; Tr[2 * i + 1] = y;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    sx = 0; sy = 0;
-    for (int i = lane; i < mT; i += GROUP) { sx += Tr[2 * i]; sy += Tr[2 * i + 1]; }
-    sx = group_sum(sx) / mT; sy = group_sum(sy) / mT;
-    vx = 0; vy = 0;
-    for (int i = lane; i < mT; i += GROUP) {
-        vx += (Tr[2 * i] - sx) * (Tr[2 * i] - sx);
-        vy += (Tr[2 * i + 1] - sy) * (Tr[2 * i + 1] - sy);
-    }
-    vx = group_sum(vx); vy = group_sum(vy);
-    const double b0 = fmax(1e-6, mT > 1 ? sqrt(vx / (mT - 1)) : 1.0);
-    const double b1 = fmax(1e-6, mT > 1 ? sqrt(vy / (mT - 1)) : 1.0);
+    thx::wave_mem_sync();
+    double mu[2], ss[2];
+    group_moments<2>(Tr, mT, lane, mu, ss);
+    const double b0 = fmax(1e-6, mT > 1 ? sqrt(ss[0] / (mT - 1)) : 1.0);
+    const double b1 = fmax(1e-6, mT > 1 ? sqrt(ss[1] / (mT - 1)) : 1.0);
     double tot = 0.0;
     for (int i = lane; i < mT; i += GROUP) {
-        const double u = (Tr[2 * i] - sx) / b0, v = (Tr[2 * i + 1] - sy) / b1;
+        const double u = (Tr[2 * i] - mu[0]) / b0, v = (Tr[2 * i + 1] - mu[1]) / b1;
         const double p = exp(-(u * u + v * v) / 2) / (2 * M_PI * b0 * b1);
         const double x = 1.0 / fmax(p, 1e-300);
         pTl[i] = x;
@@ -1276,9 +1188,7 @@ __global__ void __launch_bounds__(256) k_pf_perturb(int nImg, int mR, int mT,
         if (nSym) thx::sym_counterpart(c, mean, symQ, nSym);
         for (int k = 0; k < 4; k++) Q[4 * i + k] = c[k];
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    thx::wave_mem_sync();
     balance_rot(Q, mR, lane, pR + (size_t)l * mR);
 
     perturb_trans(Tr, pT + (size_t)l * mT, mT, sIn[2 * l], sIn[2 * l + 1], pf, transS, transM, rng,
@@ -1401,21 +1311,13 @@ __global__ void __launch_bounds__(256) k_pf_calvari2d(int nImg, int mR, const do
     if (l >= nImg || (done && done[l])) return;
     double mu0, mu1, k;
     infer_vms(quat + (size_t)l * mR * 4, mR, lane, mu0, mu1, k);
-    const double* Tr = trans + (size_t)l * mT * 2;
-    double sx = 0, sy = 0;
-    for (int i = lane; i < mT; i += GROUP) { sx += Tr[2 * i]; sy += Tr[2 * i + 1]; }
-    sx = group_sum(sx) / mT; sy = group_sum(sy) / mT;
-    double vx = 0, vy = 0;
-    for (int i = lane; i < mT; i += GROUP) {
-        vx += (Tr[2 * i] - sx) * (Tr[2 * i] - sx);
-        vy += (Tr[2 * i + 1] - sy) * (Tr[2 * i + 1] - sy);
-    }
-    vx = group_sum(vx); vy = group_sum(vy);
+    double mu[2], ss[2];
+    group_moments<2>(trans + (size_t)l * mT * 2, mT, lane, mu, ss);
     if (lane == 0) {
         const double k1 = fmax(kFloor, k);
         kOut[3 * l] = k1; kOut[3 * l + 1] = k1; kOut[3 * l + 2] = k1;
-        sOut[2 * l] = fmax(sFloor, mT > 1 ? sqrt(vx / (mT - 1)) : 0.0);
-        sOut[2 * l + 1] = fmax(sFloor, mT > 1 ? sqrt(vy / (mT - 1)) : 0.0);
+        sOut[2 * l] = fmax(sFloor, mT > 1 ? sqrt(ss[0] / (mT - 1)) : 0.0);
+        sOut[2 * l + 1] = fmax(sFloor, mT > 1 ? sqrt(ss[1] / (mT - 1)) : 0.0);
     }
 }
 
@@ -1455,9 +1357,7 @@ __global__ void __launch_bounds__(256) k_pf_perturb2d(int nImg, int mR, int mT,
         qmul(Q + 4 * i, d, o);
         for (int k = 0; k < 4; k++) Q[4 * i + k] = o[k];
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    thx::wave_mem_sync();
     balance_rot2d(Q, mR, lane, pR + (size_t)l * mR);
     perturb_trans(Tr, pT + (size_t)l * mT, mT, sIn[2 * l], sIn[2 * l + 1], pf, transS, transM, rng,
                   lane);
@@ -1619,12 +1519,8 @@ __global__ void k_top_by_weight(int nImg, int mR, const double* __restrict__ qua
 // (one sample, or all equal); normW.
 THX_DEV void balance_d(const double* D, int mD, int lane, double* pD)
 {
-    double m = 0.0;
-    for (int i = lane; i < mD; i += GROUP) m += D[i];
-    m = group_sum(m) / mD;
-    double v = 0.0;
-    for (int i = lane; i < mD; i += GROUP) v += (D[i] - m) * (D[i] - m);
-    v = group_sum(v);
+    double m, v;
+    group_moments<1>(D, mD, lane, &m, &v);
     const double sd = mD > 1 ? sqrt(v / (mD - 1)) : 0.0;
     double tot = 0.0;
     for (int i = lane; i < mD; i += GROUP) {
@@ -1653,12 +1549,8 @@ __global__ void __launch_bounds__(256) k_pf_defocus(int nImg, int mD, int op, do
     if (l >= nImg || (done && done[l])) return;
     double* D = d + (size_t)l * mD;
     if (op == 2) {
-        double m = 0.0;
-        for (int i = lane; i < mD; i += GROUP) m += D[i];
-        m = group_sum(m) / mD;
-        double v = 0.0;
-        for (int i = lane; i < mD; i += GROUP) v += (D[i] - m) * (D[i] - m);
-        v = group_sum(v);
+        double m, v;
+        group_moments<1>(D, mD, lane, &m, &v);
         if (lane == 0) sd[l] = mD > 1 ? sqrt(v / (mD - 1)) : 0.0;
         return;
     }
@@ -1668,9 +1560,7 @@ __global__ void __launch_bounds__(256) k_pf_defocus(int nImg, int mD, int op, do
         const double g = rng.gauss2().x;
         D[i] = (op == 0 ? 1.0 : D[i]) + g * scale;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    thx::wave_mem_sync();
     balance_d(D, mD, lane, pD + (size_t)l * mD);
 }
 

@@ -323,9 +323,7 @@ __global__ void __launch_bounds__(256) k_pf_symmetrise(int nImg, int mR, double*
         const int idx = (int)(rng.uniform() * mR) % mR;
         for (int k = 0; k < 4; k++) a[k] = Q[4 * idx + k];
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    thx::wave_mem_sync();
     for (int i = lane; i < mR; i += SYM_GROUP) thx::sym_counterpart(Q + 4 * i, a, sQ, nSym);
 }
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Bit identity of the map-level entry points across two builds of the library
-(csrc/volume.h's shared pieces, thx::bind_plans, the moved macros): every row
+(csrc/volume.h's shared pieces, thx::bind_plans, the moved macros) and of the
+particle statistics' (the thx_pf_* rows, --only thx_pf_ for those): every row
 runs twice in this process with the library THX_LIB names, on fixed inputs, and
 the first run's output tensors go to an .npz; --compare puts two such files
 side by side, one JSON line per row.
@@ -199,6 +200,90 @@ def rows():
         check(L.thx_TranslateI(0, P(V), -1.7, 2.25, 0.6, r, dim), "TranslateI")
         return {"V": V}
     out.append(("thx_TranslateI dim=32 r=12", translate))
+
+    # ---- the particle statistics' entry points (csrc/optimiser.hip), on the
+    # smallest clouds at which their shared pieces can go wrong: 33 images
+    # (several per wave, the last wave part full); 8 lanes per image hold 16
+    # particles each, so mR covers lanes with no particle, a part-full last
+    # lane, the register path exactly full (128) and the strided path past it
+    nI, MR, MT, MD = 33, (1, 7, 8, 9, 125, 128, 129, 200), (1, 2, 9, 151), (1, 2, 9)
+    KINDS = ("3deg", "40deg", "runs", "equal")
+
+    def cloud(kind, m, two_d):
+        """[nI, m, 4] rotations: clustered at 3 / 40 degrees, a few ancestors
+        repeated in sorted order (as a gather leaves them), or one repeated"""
+        g = np.random.default_rng([77, m, KINDS.index(kind), int(two_d)])
+        n = {"runs": min(m, 5), "equal": 1}.get(kind, m)
+        spread = 40.0 if kind == "40deg" else 3.0
+        if two_d:
+            th = g.uniform(0, 2 * np.pi, (nI, 1)) + g.standard_normal((nI, n)) * np.radians(spread)
+            q = np.stack([np.cos(th), np.sin(th), np.zeros_like(th), np.zeros_like(th)], axis=-1)
+        else:
+            q = synth.clustered_quaternions(nI, n, spread, g)
+        idx = np.sort(g.integers(0, n, size=(nI, m)), axis=1)
+        return np.take_along_axis(q, idx[..., None].repeat(4, -1), axis=1) if n < m else q
+
+    def shifts(mT):
+        return np.random.default_rng([78, mT]).standard_normal((nI, mT, 2)) * 2.0
+
+    def f64(*shape):
+        return torch.empty(*shape, dtype=torch.float64, device=dev)
+
+    for two_d in (False, True):
+        for m in MR:
+            for kind in KINDS:
+                def vari(two_d=two_d, m=m, kind=kind):
+                    q, res = T_(cloud(kind, m, two_d)), {}
+                    for mT in MT:
+                        t = T_(shifts(mT))
+                        if two_d:
+                            k, sd = f64(nI, 3), f64(nI, 2)
+                            check(L.thx_pf_calvari2d(nI, m, _ptr(q), mT, _ptr(t), 0.0, 0.0, _ptr(k),
+                                                     _ptr(sd), None), "thx_pf_calvari2d")
+                        else:
+                            k, sd = ops.pf_calvari(q, t)
+                        res[f"k mT={mT}"], res[f"sd mT={mT}"] = host(k), host(sd)
+                    return res
+                out.append((f"thx_pf_calvari{'2d' if two_d else ''} mR={m} {kind}", vari))
+
+                def perturb(two_d=two_d, m=m, kind=kind):
+                    c, res = cloud(kind, m, two_d), {}
+                    k = T_(np.tile([0.02, 0.01, 0.03], (nI, 1)))
+                    sd = T_(np.tile([1.5, 2.0], (nI, 1)))
+                    for mT in MT:       # transM 4: some translations are re-centred
+                        q, t = T_(c), T_(shifts(mT))
+                        if two_d:
+                            pR, pT = f64(nI, m), f64(nI, mT)
+                            check(L.thx_pf_perturb2d(nI, m, mT, _ptr(q), _ptr(t), _ptr(pR), _ptr(pT),
+                                                     _ptr(k), _ptr(sd), 1.0, 2.0, 4.0, SEED, 3, None),
+                                  "thx_pf_perturb2d")
+                        else:
+                            pR, pT = ops.pf_perturb(q, t, T_(c[:, 0]), k, sd, 1.0, 2.0, 4.0, SEED, 3)
+                        res.update({f"{n} mT={mT}": host(v)
+                                    for n, v in (("quat", q), ("trans", t), ("pR", pR), ("pT", pT))})
+                    return res
+                out.append((f"thx_pf_perturb{'2d' if two_d else ''} mR={m} {kind}", perturb))
+
+                if not two_d:
+                    out.append((f"thx_pf_balance_rot mR={m} {kind}", lambda m=m, kind=kind: {
+                        "pR": host(ops.pf_balance_rot(T_(cloud(kind, m, False))))}))
+
+    for mD in MD:
+        for kind in ("spread", "equal"):
+            def defocus(mD=mD, kind=kind):
+                g = np.random.default_rng([79, mD])
+                d0 = 1.02 + (0.05 * g.standard_normal((nI, mD)) if kind == "spread" else np.zeros((nI, mD)))
+                res = {}
+                d, pD, sd = f64(nI, mD), f64(nI, mD), f64(nI)
+                ops.pf_defocus("init", d, pD, arg=0.05, seed=SEED, stream_id=5)
+                res["init d"], res["init pD"] = host(d), host(pD)
+                d = T_(d0)
+                ops.pf_defocus("vari", d, sd=sd)
+                res["vari sd"] = host(sd)
+                ops.pf_defocus("perturb", d, pD, sd, arg=0.7, seed=SEED, stream_id=6)
+                res["perturb d"], res["perturb pD"] = host(d), host(pD)
+                return res
+            out.append((f"thx_pf_defocus ops 0, 2, 1 mD={mD} {kind}", defocus))
     return out
 
 
@@ -206,12 +291,14 @@ def same(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
-def dump(path):
+def dump(path, only=""):
     import torch
     if not torch.cuda.is_available():
         sys.exit("volume_identity: no GPU")
     saved = {}
     for name, thunk in rows():
+        if not name.startswith(only):
+            continue
         one, two = thunk(), thunk()
         torch.cuda.synchronize()
         rep = sorted(one) == sorted(two) and all(same(one[k], two[k]) for k in one)
@@ -258,9 +345,10 @@ def main():
     ap.add_argument("--dump")
     ap.add_argument("--compare", nargs=2)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "volume_helpers_identity.jsonl"))
+    ap.add_argument("--only", default="", help="dump the rows whose name starts with this")
     a = ap.parse_args()
     if a.dump:
-        dump(a.dump)
+        dump(a.dump, a.only)
     elif a.compare:
         sys.exit(compare(a.compare[0], a.compare[1], a.out))
     else:
