@@ -986,7 +986,12 @@ int thx_pf_top_copy(int nImg, const double* src, long lds, const int* top, doubl
  * thx_class_count -- count[cls[l]] += 1 for every image (count nK doubles the
  *   caller zeroes; it accumulates over calls, batch after batch): the
  *   numerator of refreshClassDistr (:5484-5516).  A class outside [0, nK) is
- *   not counted and is no error. */
+ *   not counted and is no error.
+ * thx_pf_score -- Particle::compressR / calScore (src/Particle.cpp:647-678,
+ *   1144-1147) of every image from its row of vari nImg x 6 {k1 k2 k3 s0 s1
+ *   sD}: score[l] = (k1 k2 k3)^(-1/6), or 1 / k1 with twoD = 1.  The last
+ *   column of saveDatabase's table, and the grading weight of the insert
+ *   (w = compressR() / mReco, src/Optimiser.cpp:6762-6763, 6972-6977). */
 int thx_rank1st_diff(int nImg, const double* topQuat, double* prevQuat, double* diffR,
                      const double* topTrans, double* prevTrans, double* diffT,
                      const double* topD, double* prevD, double* diffD, const int* cls,
@@ -994,6 +999,46 @@ int thx_rank1st_diff(int nImg, const double* topQuat, double* prevQuat, double* 
 int thx_recentre(int nImg, int idim, const float* oriFT, float* imgFT, double* topTrans,
                  double* offS, int mLT, double* trans, double* prevTrans, thx_stream_t stream);
 int thx_class_count(int nImg, const int* cls, int nK, double* count, thx_stream_t stream);
+int thx_pf_score(int nImg, const double* vari, int twoD, double* score, thx_stream_t stream);
+
+/* ------------------------------------------- starting from a .thu table ---
+ * thx_pf_load -- Particle::load (src/Particle.cpp:401-556), MODE_3D, of every
+ * image at once: what Optimiser::loadParticles (src/Optimiser.cpp:5312-5384)
+ * builds from a table row when the run does not begin with a global search.
+ * Device pointers, FP64; stream-ordered (three launches), no host wait.  Per
+ * image l:
+ *   quat[l][i] = p_i (s_i topQuat_l), a Hamilton product with the perturbation
+ *     on the left; p_i the normalised draw (g0, g1 sqrt k1, g2 sqrt k2,
+ *     g3 sqrt k3) (sampleACG; the k are not capped), s_i = +-1 by a uniform on
+ *     (-1, 1), >= 0 giving +.  topQuat is used as given (not renormalised) and
+ *     no symmetry copy is taken.
+ *   trans[l][i] = topTrans_l + (g0 sd_l0, g1 sd_l1);  d[l][i] = topD_l + g sdD_l.
+ *   pR = balanceWeight(PAR_R) as thx_pf_balance_rot gives it on that cloud;
+ *   pT = balanceWeight(PAR_T) with thx_pf_perturb's floors (sample sd >= 1e-6,
+ *     sd = 1 for a single particle, pdf >= 1e-300);  pD = balanceWeight(PAR_D),
+ *     uniform when the sample sd is 0 or mD == 1.
+ *   vari[l] = {k1 k2 k3 s0 s1 sD} (may be NULL): thx_pf_calvari's values with
+ *     both floors 0, and gsl_stats_sd of d (0 at mD <= 1).
+ * topQuat nImg x 4, k nImg x 3, topTrans / sd nImg x 2, topD / sdD nImg; quat
+ * nImg x mR x 4, trans nImg x mT x 2, pR nImg x mR, pT nImg x mT, d / pD nImg x
+ * mD.  topD, sdD, d and pD are NULL if and only if mD == 0.  sd = 0 / sdD = 0
+ * keep every sample at the top value (uniform priors through the floors);
+ * k = (0, 0, 0) collapses the cloud to +-topQuat and the statistics then divide
+ * as the reference's do.
+ * Draws: image l owns 8 lanes; lane j owns the counter stream (seed; l,
+ * stream_id, j) and the particles i = j (mod 8) of every set in rising order.
+ * The lane draws its rotations first (four uniforms each: two Box-Muller
+ * pairs, thx_pf_perturb's layout), then its translations (one pair each),
+ * then its defocus factors (one pair each, the cosine branch), then one sign
+ * uniform per rotation.  Image l's result depends on its own row and (seed,
+ * l, stream_id) only.
+ * THX_ERR_ARG before anything is enqueued: nImg < 0, mR <= 0, mT <= 0, mD < 0,
+ * a NULL required pointer, the defocus pointers given in part or against mD.
+ * nImg == 0 is a no-op. */
+int thx_pf_load(int nImg, int mR, int mT, int mD, const double* topQuat, const double* k,
+                const double* topTrans, const double* sd, const double* topD, const double* sdD,
+                unsigned long long seed, unsigned stream_id, double* quat, double* trans,
+                double* pR, double* pT, double* d, double* pD, double* vari, thx_stream_t stream);
 
 /* ------------------------------------------------------- noise model ---
  * What Optimiser::maximization (src/Optimiser.cpp:3405-3559) does next to

@@ -68,6 +68,10 @@ bool step_plan_build(const int* pxOrder, int nOrd, const float* dat, const float
                      int nImg, int nD, int* cOrd, int* plan, hipStream_t s, int* status);
 bool phase_routed(int volLayout, int pf, int nPxl, int nD);
 
+// ---- optimiser.hip: calVari (floors 0) into rows {k1 k2 k3 s0 s1 .} of vari nImg x 6
+int pf_calvari_vari(int nImg, int mR, const double* quat, int mT, const double* trans,
+                    double* vari, hipStream_t s);
+
 // ---- twod.hip: MODE_2D projection and phase
 int project2d_launch(const float* vol, int vdim, int pf, const double* rot, int rotStride, int nR,
                      const int* iCol, const int* iRow, int nPxl, float* rotP, hipStream_t s);

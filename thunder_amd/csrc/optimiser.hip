@@ -37,6 +37,7 @@
 #include <utility>
 
 #include "internal.h"
+#include "pf_group.h"
 #include "symmetry.h"
 
 // max iCol^2 + iRow^2 over the pixel set (one workgroup)
@@ -179,42 +180,6 @@ THX_DEV double quad10(const double* Mp, const double* q)
         s += q[j] * a;
     }
     return s;
-}
-
-// Particle statistics run one image per GROUP lanes (8 images per wave): the
-// 4x4 algebra is repeated by every lane anyway, so narrower groups mean
-// fewer waves for the same latency-bound FP64 chains, and each lane's 16
-// register-resident particles give the fixed point's quadratic forms ILP.
-// Measured on 12 500 x 125 (tools/pf_bench.py, profiles/r02_pf_group_ab.jsonl):
-// calVari 0.145 / 0.105 ms at GROUP 16 / 8 on 3-degree clouds, 32 and 64 slower.
-constexpr int GROUP = 8;
-
-// v from another lane of the row by DPP (both 32-bit halves)
-template <int CTRL>
-THX_DEV double dpp_d(double v)
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    // every lane's source lies inside its row: no 'old' operand to initialise
-    const int lo = __builtin_amdgcn_mov_dpp((int)(unsigned)b, CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_mov_dpp((int)(unsigned)(b >> 32), CTRL, 0xf, 0xf, true);
-    return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
-}
-
-// Sum over the GROUP lanes of an image, the same value in every lane.  For
-// GROUP 8 by DPP (quad pairs, quad halves, then the row's half mirror pairs
-// the two quads): VALU moves instead of three dependent ds_bpermute rounds
-// per value, 11 values per fixed-point pass.
-THX_DEV double group_sum(double v)
-{
-    if constexpr (GROUP == 8) {
-        v += dpp_d<0xb1>(v);    // quad_perm [1, 0, 3, 2]
-        v += dpp_d<0x4e>(v);    // quad_perm [2, 3, 0, 1]
-        v += dpp_d<0x141>(v);   // row_half_mirror: lane i <-> 7 - i of its 8
-        return v;
-    }
-#pragma unroll
-    for (int o = GROUP / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // inferACG(dmat44&, const dmat4&), DirectionalStat.cpp:93-145: Tyler's fixed
@@ -507,28 +472,29 @@ THX_DEV void calvari_acg_impl(const double* Q, int m, int lane, double* __restri
     }
 }
 
-// Mean and sum of squared deviations from it (gsl_stats_mean, and what
-// gsl_stats_sd_m divides by n - 1) of each of the C interleaved components
-// of the n samples x[C i + c], over the GROUP lanes of an image: every lane
-// gets both.  The callers floor and divide, each in its own way.
-template <int C>
-THX_DEV void group_moments(const double* x, int n, int lane, double* mean, double* ss)
-{
-    for (int c = 0; c < C; c++) mean[c] = 0.0;
-    for (int i = lane; i < n; i += GROUP)
-        for (int c = 0; c < C; c++) mean[c] += x[C * i + c];
-    for (int c = 0; c < C; c++) mean[c] = group_sum(mean[c]) / n;
-    for (int c = 0; c < C; c++) ss[c] = 0.0;
-    for (int i = lane; i < n; i += GROUP)
-        for (int c = 0; c < C; c++) ss[c] += (x[C * i + c] - mean[c]) * (x[C * i + c] - mean[c]);
-    for (int c = 0; c < C; c++) ss[c] = group_sum(ss[c]);
-}
-
 // Particle::calVari (src/Particle.cpp:1004-1121), 3D: R -- de-mean by the
 // ACG principal axis (PARTICLE_ROT_MEAN_USING_STAT_CAL_VARI), k_j =
 // A(j, j) / A(0, 0) of inferACG on the de-meaned cloud (:184-222), floored at
 // kFloor; T -- sample standard deviations (gsl_stats_sd), floored at sFloor
 // (the reseed floors of src/Optimiser.cpp:1033-1079).
+// One image's calVari on its GROUP lanes: kOut[0..2] and sOut[0..1] are the
+// image's own slots (lane 0 writes them).
+THX_DEV void calvari_image(const double* Q, int mR, const double* Tr, int mT, int lane,
+                           double kFloor, double sFloor, double* __restrict__ kOut,
+                           double* __restrict__ sOut, double* __restrict__ h)
+{
+    double A[16];
+    if (mR <= GROUP * QREG) calvari_acg_impl<true>(Q, mR, lane, h, A);
+    else calvari_acg_impl<false>(Q, mR, lane, h, A);
+    double mu[2], ss[2];
+    group_moments<2>(Tr, mT, lane, mu, ss);
+    if (lane == 0) {
+        for (int j = 1; j < 4; j++) kOut[j - 1] = fmax(kFloor, A[5 * j] / A[0]);
+        sOut[0] = fmax(sFloor, mT > 1 ? sqrt(ss[0] / (mT - 1)) : 0.0);
+        sOut[1] = fmax(sFloor, mT > 1 ? sqrt(ss[1] / (mT - 1)) : 0.0);
+    }
+}
+
 __global__ void __launch_bounds__(256) k_pf_calvari(int nImg, int mR, const double* __restrict__ quat,
                                                     int mT, const double* __restrict__ trans,
                                                     double kFloor, double sFloor,
@@ -540,18 +506,23 @@ __global__ void __launch_bounds__(256) k_pf_calvari(int nImg, int mR, const doub
     const int l = (blockIdx.x * 256 + threadIdx.x) / GROUP;
     const int lane = threadIdx.x % GROUP;
     if (l >= nImg || (done && done[l])) return;
-    const double* Q = quat + (size_t)l * mR * 4;
-    double A[16];
-    double* h = hist + (size_t)l * ACG_HIST;
-    if (mR <= GROUP * QREG) calvari_acg_impl<true>(Q, mR, lane, h, A);
-    else calvari_acg_impl<false>(Q, mR, lane, h, A);
-    double mu[2], ss[2];
-    group_moments<2>(trans + (size_t)l * mT * 2, mT, lane, mu, ss);
-    if (lane == 0) {
-        for (int j = 1; j < 4; j++) kOut[3 * l + j - 1] = fmax(kFloor, A[5 * j] / A[0]);
-        sOut[2 * l] = fmax(sFloor, mT > 1 ? sqrt(ss[0] / (mT - 1)) : 0.0);
-        sOut[2 * l + 1] = fmax(sFloor, mT > 1 ? sqrt(ss[1] / (mT - 1)) : 0.0);
-    }
+    calvari_image(quat + (size_t)l * mR * 4, mR, trans + (size_t)l * mT * 2, mT, lane, kFloor,
+                  sFloor, kOut + 3 * l, sOut + 2 * l, hist + (size_t)l * ACG_HIST);
+}
+
+// calVari without floors into rows {k1 k2 k3 s0 s1 .} of vari nImg x 6 (what
+// Particle::vari reports; slot 5, the defocus spread, is the caller's)
+__global__ void __launch_bounds__(256) k_pf_calvari_vari(int nImg, int mR,
+                                                         const double* __restrict__ quat, int mT,
+                                                         const double* __restrict__ trans,
+                                                         double* __restrict__ vari,
+                                                         double* __restrict__ hist)
+{
+    const int l = (blockIdx.x * 256 + threadIdx.x) / GROUP;
+    const int lane = threadIdx.x % GROUP;
+    if (l >= nImg) return;
+    calvari_image(quat + (size_t)l * mR * 4, mR, trans + (size_t)l * mT * 2, mT, lane, 0.0, 0.0,
+                  vari + 6 * (size_t)l, vari + 6 * (size_t)l + 3, hist + (size_t)l * ACG_HIST);
 }
 
 // Particle::balanceWeight(PAR_R), 3D (src/Particle.cpp:2330-2340):
@@ -1110,20 +1081,7 @@ THX_DEV void perturb_trans(double* Tr, double* pTl, int mT, double s0, double s1
         Tr[2 * i] = x; Tr[2 * i + 1] = y;
     }
     thx::wave_mem_sync();
-    double mu[2], ss[2];
-    group_moments<2>(Tr, mT, lane, mu, ss);
-    const double b0 = fmax(1e-6, mT > 1 ? sqrt(ss[0] / (mT - 1)) : 1.0);
-    const double b1 = fmax(1e-6, mT > 1 ? sqrt(ss[1] / (mT - 1)) : 1.0);
-    double tot = 0.0;
-    for (int i = lane; i < mT; i += GROUP) {
-        const double u = (Tr[2 * i] - mu[0]) / b0, v = (Tr[2 * i + 1] - mu[1]) / b1;
-        const double p = exp(-(u * u + v * v) / 2) / (2 * M_PI * b0 * b1);
-        const double x = 1.0 / fmax(p, 1e-300);
-        pTl[i] = x;
-        tot += x;
-    }
-    tot = group_sum(tot);
-    for (int i = lane; i < mT; i += GROUP) pTl[i] /= tot;
+    balance_trans(Tr, pTl, mT, lane);
 }
 
 // Particle::perturb + balanceWeight for one image per GROUP lanes
@@ -1514,25 +1472,6 @@ __global__ void k_top_by_weight(int nImg, int mR, const double* __restrict__ qua
 }
 
 // ---- defocus particles (PAR_D) of a CTF search, one image per GROUP lanes.
-// balanceWeight(PAR_D) (src/Particle.cpp:2374-2409): w_i = 1 / N(d_i - m; s)
-// with the sample mean m and s = gsl_stats_sd_m (n - 1), 1 when s == 0
-// (one sample, or all equal); normW.
-THX_DEV void balance_d(const double* D, int mD, int lane, double* pD)
-{
-    double m, v;
-    group_moments<1>(D, mD, lane, &m, &v);
-    const double sd = mD > 1 ? sqrt(v / (mD - 1)) : 0.0;
-    double tot = 0.0;
-    for (int i = lane; i < mD; i += GROUP) {
-        const double u = (D[i] - m) / sd;
-        const double x = sd == 0.0 ? 1.0 : 1.0 / (exp(-0.5 * u * u) / (sd * sqrt(2 * M_PI)));
-        pD[i] = x;
-        tot += x;
-    }
-    tot = group_sum(tot);
-    for (int i = lane; i < mD; i += GROUP) pD[i] /= tot;
-}
-
 // op 0: initD (src/Particle.cpp:281-310, PARTICLE_DEFOCUS_INIT_GAUSSIAN):
 //       d_i = 1 + N(0, arg), balanceWeight;
 // op 1: perturb(arg, PAR_D) (:1278-1288): d_i += N(0, sd[l]) arg, balanceWeight;
@@ -1549,9 +1488,8 @@ __global__ void __launch_bounds__(256) k_pf_defocus(int nImg, int mD, int op, do
     if (l >= nImg || (done && done[l])) return;
     double* D = d + (size_t)l * mD;
     if (op == 2) {
-        double m, v;
-        group_moments<1>(D, mD, lane, &m, &v);
-        if (lane == 0) sd[l] = mD > 1 ? sqrt(v / (mD - 1)) : 0.0;
+        const double s = defocus_sd(D, mD, lane);
+        if (lane == 0) sd[l] = s;
         return;
     }
     Philox rng(seed, (uint32_t)l, stream, 0xde00u | (uint32_t)lane);
@@ -1816,6 +1754,21 @@ extern "C" int thx_pf_calvari(int nImg, int mR, const double* quat, int mT, cons
     THX_HIP(hipMallocAsync(reinterpret_cast<void**>(&hist), sizeof(double) * nImg * ACG_HIST, s));
     hipLaunchKernelGGL(k_pf_calvari, dim3(thx::cdiv(nImg * GROUP, 256)), dim3(256), 0, s, nImg, mR,
                        quat, mT, trans, kFloor, sFloor, k, sd, nullptr, hist);
+    const hipError_t e = hipGetLastError();
+    THX_HIP(hipFreeAsync(hist, s));
+    THX_HIP(e);
+    return THX_OK;
+}
+
+// thx_pf_calvari with kFloor = sFloor = 0 into vari nImg x 6 (slots 0 .. 4), for
+// Particle::load (load.hip); the arguments are the caller's to validate
+int thx::pf_calvari_vari(int nImg, int mR, const double* quat, int mT, const double* trans,
+                         double* vari, hipStream_t s)
+{
+    double* hist = nullptr;
+    THX_HIP(hipMallocAsync(reinterpret_cast<void**>(&hist), sizeof(double) * nImg * ACG_HIST, s));
+    hipLaunchKernelGGL(k_pf_calvari_vari, dim3(thx::cdiv(nImg * GROUP, 256)), dim3(256), 0, s, nImg,
+                       mR, quat, mT, trans, vari, hist);
     const hipError_t e = hipGetLastError();
     THX_HIP(hipFreeAsync(hist, s));
     THX_HIP(e);

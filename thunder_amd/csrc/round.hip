@@ -3,7 +3,9 @@
 //   thx_rank1st_diff -- Particle::diffTopR / diffTopT / diffTopD / diffTopC
 //                       (src/Particle.cpp:2004-2038) of every image;
 //   thx_recentre     -- Optimiser::reCentreImg (src/Optimiser.cpp:6064-6090);
-//   thx_class_count  -- the numerator of refreshClassDistr (:5386-5432).
+//   thx_class_count  -- the numerator of refreshClassDistr (:5386-5432);
+//   thx_pf_score     -- Particle::compressR / calScore (src/Particle.cpp:647-678,
+//                       1144-1147), the table's score and the grading weight.
 // Nothing here synchronises or allocates; every pointer is a device pointer.
 #include "common.h"
 
@@ -124,6 +126,17 @@ __global__ void __launch_bounds__(256) k_class_count(int nImg, const int* __rest
     if (k >= 0 && k < nK) atomicAdd(count + k, 1.0);
 }
 
+// compressR of every image from its row {k1 k2 k3 s0 s1 sD} of vari:
+// (k1 k2 k3)^(-1/6) in 3D, 1 / k1 in MODE_2D
+__global__ void __launch_bounds__(256) k_pf_score(int nImg, const double* __restrict__ vari,
+                                                  int twoD, double* __restrict__ score)
+{
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    if (l >= nImg) return;
+    const double* v = vari + 6 * (size_t)l;
+    score[l] = twoD ? 1.0 / v[0] : pow(v[0] * v[1] * v[2], -1.0 / 6);
+}
+
 }  // namespace
 
 extern "C" int thx_rank1st_diff(int nImg, const double* topQuat, double* prevQuat, double* diffR,
@@ -177,5 +190,16 @@ extern "C" int thx_class_count(int nImg, const int* cls, int nK, double* count,
     THX_CHECK_ARG(cls && count, "thx_class_count: null argument");
     THX_LAUNCH(k_class_count, dim3(thx::cdiv(nImg, 256)), dim3(256), 0, thx::as_stream(stream),
                nImg, cls, nK, count);
+    return THX_OK;
+}
+
+extern "C" int thx_pf_score(int nImg, const double* vari, int twoD, double* score,
+                            thx_stream_t stream)
+{
+    THX_CHECK_ARG(nImg >= 0 && (twoD == 0 || twoD == 1), "thx_pf_score: nImg < 0 or twoD not 0 / 1");
+    if (nImg == 0) return THX_OK;
+    THX_CHECK_ARG(vari && score, "thx_pf_score: null argument");
+    THX_LAUNCH(k_pf_score, dim3(thx::cdiv(nImg, 256)), dim3(256), 0, thx::as_stream(stream), nImg,
+               vari, twoD, score);
     return THX_OK;
 }
