@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 import torch
 
+from scan_ref import dvp64
 from thunder_amd import synth
 
 N, PF, RU, RL = 256, 2, 24, 1
@@ -51,15 +52,9 @@ def c3_budget_stack(orc, vol, px, gset, rsel, snr, nImg, seed):
 
 def dvp_float64(P, Tt, dat, ctf, sig):
     """sum_i s |d - c (T P)|^2 in float64 from FP32 operands: P [nR, nPxl],
-    Tt [nT, nPxl] complex, images [nImg, nPxl]; -> [nImg, nR, nT]."""
-    P, Tt = P.astype(np.complex128), Tt.astype(np.complex128)
-    out = np.empty((len(dat), len(P), len(Tt)))
-    for l in range(len(dat)):
-        d, c, s = dat[l].astype(np.complex128), ctf[l].astype(np.float64), sig[l].astype(np.float64)
-        for r in range(len(P)):
-            e = d[None, :] - c[None, :] * (Tt * P[r][None, :])
-            out[l, r] = (s[None, :] * (e.real ** 2 + e.imag ** 2)).sum(1)
-    return out
+    Tt [nT, nPxl] complex, images [nImg, nPxl]; -> [nImg, nR, nT]
+    (scan_ref.dvp64, the reference of the scan's edge tests too)."""
+    return dvp64(P, Tt, dat, ctf, sig)
 
 
 def marginals(d, pR, pT):
