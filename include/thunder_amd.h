@@ -1431,6 +1431,78 @@ int thx_postprocess(const float* A, const float* B, int N, int nShell, const flo
                     double* fit, double* guinier, float* average, float* sharp, void* workspace,
                     size_t wsBytes, thx_stream_t stream);
 
+/* ------------------------------------------------------------ map tools ---
+ * The stand-alone map tools on device (csrc/maptools.hip): thunder_alignZ,
+ * SYMMETRIZE_RL, thunder_resize, thunder_project and thunder_mask.  Real maps
+ * [N][N][N] float, origin at index 0, negatives wrapped; transforms
+ * half-complex [N][N][N/2+1] float2, unnormalised; N even, 16 <= N <= 1024.
+ * Every entry is stream-ordered, allocates nothing, reads nothing back, uses
+ * no atomics (bit-identical from run to run) and rejects bad arguments before
+ * any device work.
+ *
+ * thx_vol_transform_rl -- VOL_TRANSFORM_MAT_RL (include/Geometry/
+ *   Transformation.h:58-84) for nMat matrices in one pass: for every signed
+ *   voxel x = (i, j, k)
+ *     dst(x) = (addSrc ? src(x) : 0) + sum_m [|M_m x|^2 < r^2] interp(src, M_m x),
+ *   the matrices added in index order.  mat (device, FP64) nMat x 9 row-major,
+ *   as thx_symmetry writes R.  M x and its squared norm are FP64 in the
+ *   reference's order (m0 i + m1 j + m2 k, then x^2 + y^2 + z^2, strict <, no
+ *   fused multiply-add); the coordinate is then rounded to FP32 and the taps,
+ *   weights and sum are FP32 (Volume::getByInterpolationRL, src/Image/
+ *   Volume.cpp:296-312, 482-489: floor-based trilinear, taps in box order k,
+ *   j, i).  interp 1: trilinear; 0: nearest, rint of each coordinate.  nMat =
+ *   1, addSrc = 0, r = N/2 - 1 is thunder_alignZ's call (appsrc/
+ *   thunder_alignZ.cpp:158-162); the elements of thx_symmetry with addSrc = 1
+ *   give SYMMETRIZE_RL (Transformation.h:139-163); nMat = 0 copies (addSrc) or
+ *   clears.  0 < r <= N/2 - 1, which keeps all eight taps inside the box;
+ *   dst != src.
+ * thx_ft_resize -- thunder_resize's copy (appsrc/thunder_resize.cpp:149-163)
+ *   between half-complex maps of boxes N and M: with L = min(N, M), every
+ *   stored voxel 0 <= i <= L/2, -L/2 <= j, k < L/2 moves from its signed
+ *   position in src to the same signed position in dst; every other element of
+ *   dst is 0.  The row j = -L/2 keeps its own value (it is not mirrored to
+ *   +L/2).  A pure move: bit-exact.  dst must not overlap src.
+ * thx_vol_resize -- the tool's chain on a real map: fw at N, thx_ft_resize,
+ *   the Hermitian part of planes i = 0 and i = M/2 (all FFTW's c2r reads of
+ *   them; as thx_fsc_masked), bw at M with its 1 / M^3.  As in the reference
+ *   there is NO renormalisation: the mean of dst is (N/M)^3 times src's.  src
+ *   is left untouched.
+ * thx_vol_resize_workspace (host) -- its bytes; 0 for bad arguments.
+ * thx_project_images -- Projector::project(Image&, const dmat33&)
+ *   (src/Projector.cpp:276-294) for n rotations, then FFT::bw
+ *   (appsrc/thunder_project.cpp:187-204).  vol: a projectee as thx_projectee
+ *   makes it, vdim = pf N; mat (device, FP64) n x 9 as thx_rotmat writes it;
+ *   trans (device, FP64, may be NULL) n x 2.  For image m and stored pixel
+ *   0 <= i <= r, -r <= j < r, i^2 + j^2 < r^2:
+ *     imgFT[m](i, j) = trilinear(vol, M_m (pf i, pf j, 0)), the coordinate and
+ *   the gather as thx_project3d's, times thx_trans_table's phase exp(-2 pi i
+ *   (i tx + j ty) / N) when trans is given; every other element of imgFT [n][N]
+ *   [N/2+1] is 0.  A gather that would leave the projectee (a matrix that is
+ *   no rotation) gives a NaN pixel.  imgRL [n][N][N]: the backward transform
+ *   scaled by 1 / N^2, taken from a workspace copy whose columns i = 0 and i =
+ *   N/2 hold their Hermitian part (as thx_subtract's diffRL); centred as
+ *   thx_subtract's flag.  Either output may be NULL, not both.  1 <= r <=
+ *   N/2 - 1 (setProjectee's _maxRadius is N/2 - 1); n = 0 returns THX_OK
+ *   without a launch.
+ * thx_project_images_workspace (host) -- its bytes (the copy the C2R
+ *   consumes); 0 for bad arguments.
+ * thx_vol_soft_mask -- softMask(dst, src, r, ew, bg = 0) on a volume
+ *   (src/Functions/Mask.cpp:499-521), which is thunder_mask
+ *   (appsrc/thunder_mask.cpp:143, ew = EDGE_WIDTH_RL = 6): with u = |(i, j, k)|
+ *   in FP32, dst = src for u < r, 0 for u > r + ew, else src (1 - (0.5 - 0.5
+ *   cos((u - r) / ew pi))).  r >= 0, ew > 0, both finite.  dst may be src. */
+int thx_vol_transform_rl(const float* src, int N, const double* mat, int nMat, double r, int interp,
+                         int addSrc, float* dst, thx_stream_t stream);
+int thx_ft_resize(const float* srcFT, int N, float* dstFT, int M, thx_stream_t stream);
+size_t thx_vol_resize_workspace(int N, int M);
+int thx_vol_resize(const float* src, int N, float* dst, int M, void* workspace, size_t wsBytes,
+                   thx_stream_t stream);
+size_t thx_project_images_workspace(int n, int N);
+int thx_project_images(const float* vol, int vdim, int pf, const double* mat, const double* trans,
+                       int n, int N, int r, float* imgFT, float* imgRL, int centred,
+                       void* workspace, size_t wsBytes, thx_stream_t stream);
+int thx_vol_soft_mask(const float* src, int N, float r, float ew, float* dst, thx_stream_t stream);
+
 /* HIP event pairs for thx_expect_cfg.phaseEvents: create n (begin, end)
  * pairs, read back ms[i] per pair (-1: not recorded), destroy. */
 int thx_event_pairs_create(int n, void** events);

@@ -58,14 +58,6 @@ constexpr int RF_WAVES = 4;
 constexpr int RF_THREADS = 64 * RF_WAVES;
 constexpr int RF_RSTEP = RF_THREADS / RF_CT;
 
-// softMask's weight of the source (1 - w, bg = 0) at distance u
-THX_DEV float soft_mask(float u, float r, float ew)
-{
-    if (u > r + ew) return 0.f;
-    if (u >= r) return 1.f - (0.5f - 0.5f * cosf((u - r) / ew * (float)M_PI));
-    return 1.f;
-}
-
 // 1 / TIK_RL(u / pv) (interp 0) or 1 / NIK_RL(u / pv) (interp 1), pv = pf vdim
 THX_DEV float grid_corr(float u, float pv, int interp)
 {

@@ -277,6 +277,22 @@ bool box_ok(int N) { return N > 0 && N % 2 == 0 && N <= 4096; }
 
 }  // namespace
 
+int thx::hermitian_cols(float2* ft, size_t nPlane, int N, hipStream_t s)
+{
+    const size_t nCol = nPlane * (size_t)(N + 2);
+    THX_LAUNCH(k_hermitian_cols, dim3(nCol > 2048 * 256 ? 2048 : thx::cdiv((long)nCol, 256)),
+               dim3(256), 0, s, ft, nPlane, N);
+    return THX_OK;
+}
+
+int thx::rl_finish(float* rl, size_t nPlane, int nImg, int N, int centred, float scale,
+                   const int* cls, int nK, hipStream_t s)
+{
+    THX_LAUNCH(k_rl_finish, dim3(2048), dim3(256), 0, s, rl, nPlane, nImg, N, centred, scale, cls,
+               nK);
+    return THX_OK;
+}
+
 extern "C" size_t thx_region_centroid_workspace(int N)
 {
     if (!box_ok(N)) return 0;

@@ -91,6 +91,14 @@ THX_DEV double sum_slots(const double* __restrict__ part, int nBlock, int nTab, 
     return t;
 }
 
+// softMask's weight of the source (1 - w, bg = 0) at distance u
+THX_DEV float soft_mask(float u, float r, float ew)
+{
+    if (u > r + ew) return 0.f;
+    if (u >= r) return 1.f - (0.5f - 0.5f * cosf((u - r) / ew * (float)M_PI));
+    return 1.f;
+}
+
 // resP(curve, thres, 1, 1, false) (src/Functions/Spectrum.cpp:339-363): the first shell from 1
 // whose value is below thres, minus one (the trailing result--); thres is the reference's
 // RFLOAT, widened for the compare
@@ -131,5 +139,15 @@ inline unsigned stream_blocks(size_t n, int threads, unsigned cap)
 // planes i = 0 and i = N/2 of a half-complex volume <- their Hermitian part, before a C2R
 // (fsc_masked.hip)
 int hermitian_planes(float2* ft, int N, hipStream_t s);
+
+// the same for nPlane half-complex images [N][N/2+1]: columns i = 0 and i = N/2 <- their
+// Hermitian part, before a batched 2D C2R (subtract.hip)
+int hermitian_cols(float2* ft, size_t nPlane, int N, hipStream_t s);
+
+// after that C2R, in place on nPlane images [N][N]: times scale, and with centred the corner
+// origin moved to the centred layout of an MRC stack; plane p is NaN when cls (may be NULL:
+// class 0) has cls[p % nImg] outside [0, nK) (subtract.hip)
+int rl_finish(float* rl, size_t nPlane, int nImg, int N, int centred, float scale, const int* cls,
+              int nK, hipStream_t s);
 
 }  // namespace thx
